@@ -7,8 +7,13 @@ TD update = t2omca_amd.learner.TDLearner.train on a synthetic batch resident
 in HBM (t2omca_amd.synthetic, SURVEY.md §8 d).  One agent-transition = one
 (episode, timestep, agent) of the sampled batch, so an update is B*T*A.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times K steps, writes the last step's outputs if
+--dump-outputs is given, and prints the line.  --full adds, after that and each
+in a run of its own, the CPU baselines, the fp32 companion of a bf16 run and
+the fp32 16-AGV update.
 
 `--gpus N` with N > 1 from a plain process starts the N ranks itself
 (torch.distributed.run on 127.0.0.1, one process per GPU, RCCL); under a
@@ -17,8 +22,8 @@ launcher (WORLD_SIZE set) each process is one rank.
 Data parallel (weak scaling): every rank trains on its own 1024-episode shard
 and the flat gradient (+ Σ mask) is all-reduced over RCCL once per update.
 Rank 0 prints ONE JSON line.  Per-kernel times come from HIP events recorded
-on the launch stream inside the timed region; the CPU baseline is the
-oracle's PyTorch-CPU TD update (oracle/ref_learner.py) on a bounded sample.
+on the launch stream inside the timed region; the CPU baseline (--full) is
+the oracle's PyTorch-CPU TD update (oracle/ref_learner.py) on a bounded sample.
 """
 import argparse
 import json
@@ -53,7 +58,18 @@ def parse():
     ap.add_argument("--dtype", choices=("bf16", "fp32"), default="bf16",
                     help="MFMA operand precision (BASELINE configs[2] is quoted in bf16; accumulation, "
                          "LayerNorm, softmax, recurrent state, TD targets and Adam stay fp32 either way)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each in a run of its own after "
+                         "the timed steps: the CPU baselines, the fp32 companion of a bf16 run and the fp32 "
+                         "16-AGV update beside configs[2] (the --no-* options below drop single ones).  "
+                         "Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="train / forward / expand modes: after the timed steps write what the last timed step "
+                         "returned to its caller (and, for a TD update, the parameters it left) "
+                         "as DIR/<name>.npy, float32 or float64, at most 64 MB in all (a larger array as a "
+                         "fixed seeded sample of its elements); inputs are seeded, so two builds run with the "
+                         "same arguments can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline legs")
     ap.add_argument("--cpu-sample", type=int, default=16, help="episodes in the CPU-baseline sample")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--mode", choices=("train", "forward", "rollout", "expand", "dropin", "loop"), default="train",
@@ -70,7 +86,7 @@ def parse():
     ap.add_argument("--compact-obs", action="store_true",
                     help="rollout mode: store obs in the compact wire format (SURVEY.md §8 f3)")
     ap.add_argument("--no-cpu-configs0", action="store_true",
-                    help="skip the configs[0]-shape (16 AGVs, T=150) CPU-baseline figure")
+                    help="--full: skip the configs[0]-shape (16 AGVs, T=150) CPU-baseline figure")
     ap.add_argument("--mecs", type=int, default=2, help="rollout mode: MEC servers")
     ap.add_argument("--rollout-precision", choices=("fp32", "bf16"), default="fp32",
                     help="rollout / loop modes: the agent step's MFMA operands (fp32 = the reference's precision)")
@@ -97,13 +113,19 @@ def parse():
                          "instrumented update, so every step would inflate ms_per_step ~1.5%%, every 5th "
                          "~0.3%%; 0: never)")
     ap.add_argument("--no-fp32-companion", dest="fp32_companion", action="store_false",
-                    help="skip the fp32-precision companion timing of the same workload (bf16 runs)")
+                    help="--full: skip the fp32-precision companion timing of the same workload (bf16 runs)")
     ap.add_argument("--no-config-companions", dest="config_companions", action="store_false",
-                    help="skip the fp32 16-AGV TD update (1024 episodes x T=150) timed beside the "
+                    help="--full: skip the fp32 16-AGV TD update (1024 episodes x T=150) timed beside the "
                          "headline (N=1, configs[2] runs only)")
     ap.add_argument("--print-workload-tag", action="store_true",
                     help="print the tag that keys profiles/hbm_traffic.json for these args and exit")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs is not None and a.mode not in ("train", "forward", "expand"):
+        ap.error(f"--dump-outputs is not available in --mode {a.mode}")
+    if not a.full:  # a plain run: the headline figure only
+        a.no_cpu_baseline, a.fp32_companion, a.config_companions = True, False, False
     # per-mode defaults: each mode's BASELINE config (SURVEY.md §8 scenario mapping)
     scen = a.mode in ("forward", "rollout", "dropin", "loop")
     if a.agents is None:
@@ -119,6 +141,28 @@ def workload_tag(args):
     if args.mode == "rollout":
         return rollout_tag(args)
     return f"b{args.batch}_t{args.T}_a{args.agents}_{args.dtype}"
+
+
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: `arrays` (name -> tensor, None entries dropped) as path/<name>.npy,
+    float64 where the tensor is, float32 otherwise (integers and bf16 included).  No
+    more than `budget` bytes in all: an array above its even share of the budget is
+    written as a sample of its flattened elements, the sorted indices drawn without
+    replacement from numpy's default_rng(0), so the same elements every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    share = budget // max(1, len(arrays))
+    for name, t in sorted(arrays.items()):
+        t = torch.as_tensor(t).detach()
+        a = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def train_config_name(A, B, T):
@@ -596,6 +640,8 @@ def expand_bench(args, world, rank, dev):
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"obs": out})
     rows = B * (T + 1) * A
     dense_b, wire_bytes = rows * 9 * A * 4, rows * 16 + B * (8 + 2 * 9 * A * 8)
     achieved = (dense_b + wire_bytes) / (kern_ms * 1e-3) / 1e9
@@ -796,8 +842,9 @@ def main():
 
         def step(i):
             q, h = ops.agent_unroll_fwd(learner.sa, learner.pack_a, batch["obs"])
-            ops.mixer_unroll_fwd(learner.sm, learner.pack_m, batch["state"], h, qmode_on=1, q_on=q, actions=act,
-                                 T_on=T, want_xout=False)
+            o = ops.mixer_unroll_fwd(learner.sm, learner.pack_m, batch["state"], h, qmode_on=1, q_on=q, actions=act,
+                                     T_on=T, want_xout=False)
+            return {"agent_q": q, "agent_h": h, **{"mixer_" + k: v for k, v in o.items() if torch.is_tensor(v)}}
     else:
         # the driver's closed step (per_run.py:224-238): the update, then the sampled
         # episodes' priorities back into the replay buffer.  --priorities device: the
@@ -815,6 +862,7 @@ def main():
                 info = lr.train(batch, 0, i, per_weight=w)
                 # per_run.py:237-238's `+ 1e-6`, applied inside the priority kernel
                 buf.update_priorities(idx, info["td_errors_abs"].flatten(), add=1e-6)
+                return info
             return step
         step = make_step(learner)
 
@@ -830,7 +878,8 @@ def main():
             learner.timer = timer if every > 0 and i % every == 0 else None
             if learner.timer is not None:
                 timer.updates += 1
-            step(i)
+            r = step(i)
+        last_out[:] = [r]  # what the last timed step handed its caller (--dump-outputs)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -850,9 +899,16 @@ def main():
         return el
 
     rank_times = []
+    last_out = []
 
     timer = KernelTimer()
     elapsed = timed(step, timer, args.kernel_timer_every)
+    if args.dump_outputs is not None and rank == 0:
+        arrays = dict(last_out[0])
+        if args.mode == "train":  # and what the update left in the caller's modules: the stepped parameters
+            arrays.update(params=learner.params)
+        dump_outputs(args.dump_outputs, arrays)
+    last_out.clear()
     if args.mode == "forward":
         value = world * B * (T + 1) * A * args.steps / elapsed
         out = {"metric": "agent-transitions/sec for agent+mixer forward (inference over a replay batch)",
@@ -894,6 +950,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "updates_done": learner.step_count,  # Adam steps the headline learner really took: warmup + steps
         "ms_per_step": ms_step,
         "higher_is_better": True,
         "scaling": "weak",

@@ -568,6 +568,17 @@ T2O_DEV void dw_run(const DwGemmArgs& a, int wg, int nwg, TT* buf0, TT* buf1, co
   if (nj > 3) dw_load<Dm, TT>(a, wg, nwg, 3, r1);
   __syncthreads();
   st.ready();
+  // Every wave's register copy of its weight fragments is complete before any
+  // wave enters the loop.  The barrier orders no store (the weight image is
+  // written once, before the barrier above); what it changes is when the
+  // fragments are read: hipcc otherwise sinks these LDS reads below init()'s
+  // n1 fold, which waits for every global load of the wave, so each wave reads
+  // them at its own time while others already run tiles.  Read that late, the
+  // lean agent contraction (bf16) is not bit-reproducible at configs[2]: one
+  // workgroup's FFN quarter 1 of block 1 (dW1 rows / dW2 columns 32..47) comes
+  // out a few ulps off in most 12-update trajectories.  Why is not established
+  // (DESIGN.md §7); tests/test_gpu_reproducibility.py holds the case.
+  __syncthreads();
   for (int64_t j = 0; j < nj; j += 2) {
     compute(buf0);
     __syncthreads();

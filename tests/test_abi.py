@@ -102,15 +102,15 @@ def test_product_path_refuses_cpu_tensors():
 
 def test_dropin_modules_state_dict_matches_reference_keys():
     """state_dict keys/shapes equal the reference modules' (checked against the golden fixture)."""
-    import glob
-
     import numpy as np
     from t2omca_amd.modules import TransformerAgent, TransformerMixer
     from t2omca_amd.synthetic import make_args
     args = make_args(8, device="cpu")
-    for cls, pat in ((TransformerAgent, "agent_a8*.npz"), (TransformerMixer, "mixer_a8*.npz")):
+    # the default network's fixtures by name: several fixtures start with agent_a8 / mixer_a8
+    # (emb 64, the other mixer heads), and a directory lists them in no fixed order
+    for cls, name in ((TransformerAgent, "agent_a8_e32_h3_d2.npz"), (TransformerMixer, "mixer_a8_e32_h3_d2.npz")):
         m = cls(None, args) if cls is TransformerAgent else cls(args)
-        z = np.load(glob.glob(os.path.join(REPO, "tests", "golden", pat))[0])
+        z = np.load(os.path.join(REPO, "tests", "golden", name))
         ref = {k[6:]: z[k].shape for k in z.files if k.startswith("param/")}
         mine = {k: tuple(v.shape) for k, v in m.state_dict().items()}
         assert list(mine) == list(ref) and mine == ref

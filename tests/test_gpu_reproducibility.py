@@ -76,3 +76,39 @@ def test_paired_contraction_equals_separate_launches(A, B, T, precision):
         out[mode] = (learner.grad.clone(), info["td_errors_abs"].clone(), learner.params.clone())
     for name, a, b in zip(("grad", "priorities", "params"), out["pair"], out["side"]):
         assert torch.equal(a, b), (name, int((a != b).sum()))
+
+
+def test_headline_update_bit_reproducible_without_syncs():
+    """configs[2] itself (8 AGVs, 1024 episodes x T = 60, bf16, the mixer's tape contraction
+    on the side stream): eight trajectories of twelve back-to-back updates from one
+    start, no host sync between the updates, give the same gradient bits at every
+    update.  Without the barrier after DwFfn::ready() in dw_run (t2o_dwgemm.hip) about
+    three of four such trajectories have one workgroup's slab of the agent contraction a
+    few ulps off at some update after the first; the smaller batches above never show it
+    (DESIGN.md §7)."""
+    require_gpu()
+    from t2omca_amd.learner import TDLearner
+    from t2omca_amd.synthetic import make_batch
+    A, B, T, K, TR = 8, 1024, 60, 12, 8
+    batch, w = make_batch(B, T, A, seed=1)
+    agent, mixer, _, _ = _setup(A, seed=5)
+    learner = TDLearner(agent, mixer, target_update_interval=10 ** 9, precision="bf16", priorities_to_cpu=False)
+    assert learner.contract == "side" and learner.overlap
+    p0 = learner.params.clone()
+    runs = []
+    for _ in range(TR):
+        learner.params.copy_(p0)
+        learner.exp_avg.zero_()
+        learner.exp_avg_sq.zero_()
+        learner.step_count = 0
+        learner._params_written()
+        torch.cuda.synchronize()
+        sums = []
+        for step in range(K):
+            learner.train(batch, 0, step, per_weight=w)
+            sums.append(learner.grad.view(torch.int32).to(torch.int64).sum().reshape(1))  # exact, order-free
+        runs.append((torch.cat(sums).cpu().tolist(), learner.params.clone()))
+    assert torch.isfinite(runs[0][1]).all()
+    differing = [i for i in range(1, TR) if runs[i][0] != runs[0][0] or not torch.equal(runs[i][1], runs[0][1])]
+    print(f"{TR} trajectories of {K} updates: {len(differing)} differ from the first")
+    assert not differing, differing

@@ -4,7 +4,7 @@
 set -eu
 OUT=gpurun_out/$1
 mkdir -p "$OUT"
-B="timeout -k 10 240 python bench.py --no-cpu-baseline"
+B="timeout -k 10 240 python bench.py --full --no-cpu-baseline"
 $B --agents 16 --batch 32 --T 150 > "$OUT/c1_train.json"
 $B --mode forward --agents 16 --batch 128 --T 150 > "$OUT/c2_fwd.json"
 $B --agents 16 --batch 1024 --T 150 --steps 5 > "$OUT/a16_train.json"

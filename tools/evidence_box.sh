@@ -27,12 +27,12 @@ for part in $PARTS; do
       timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || { tail -5 "$OUT/smoke.log"; exit 1; }
       tail -1 "$OUT/smoke.log"
       echo "== bench (no CPU legs)"
-      timeout -k 10 300 python bench.py --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
+      timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
       python -c "import json,sys;d=json.load(open(sys.argv[1]));print(round(d['value']/1e6,2),'M/s',round(d['ms_per_step'],3),'ms',d['kernels_ms'],d['roofline']['kernel'],round(d['roofline']['frac'],4))" "$OUT/bench.json"
       ;;
     bench)
       echo "== default bench (CPU baseline legs)"
-      timeout -k 10 400 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
+      timeout -k 10 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err" || { tail -5 "$OUT/bench_default.err"; exit 1; }
       python -c "import json,sys;d=json.load(open(sys.argv[1]));print(round(d['value']/1e6,2),'M/s',d['ms_per_step'],d['cpu_baseline'])" "$OUT/bench_default.json"
       ;;
     prof) echo "== profile"; bash tools/profile_box.sh "$TAG/prof" || exit 1 ;;

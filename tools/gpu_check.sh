@@ -8,9 +8,9 @@ mkdir -p "$OUT"
 timeout -k 10 400 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > "$OUT/pytest.log" 2>&1 \
   || { tail -30 "$OUT/pytest.log"; exit 1; }
 tail -2 "$OUT/pytest.log"
-timeout -k 10 200 python bench.py --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"
-timeout -k 10 200 python bench.py --no-cpu-baseline --dtype fp32 > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"
-timeout -k 10 200 python bench.py --no-cpu-baseline --serial > "$OUT/bench_bf16_serial.json" 2> "$OUT/bench_bf16_serial.err"
+timeout -k 10 200 python bench.py --full --no-cpu-baseline > "$OUT/bench_bf16.json" 2> "$OUT/bench_bf16.err"
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --dtype fp32 > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --serial > "$OUT/bench_bf16_serial.json" 2> "$OUT/bench_bf16_serial.err"
 python - "$OUT" <<'PY'
 import json, sys
 for d in ("bf16", "fp32", "bf16_serial"):
