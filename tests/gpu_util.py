@@ -117,3 +117,83 @@ def oracle_td_tie_aware(pa, pm, cfg, batch, w, gpu_grad=None, margin=1e-6, pa_tg
     assert all(u is not None and u <= TIE_ULPS for u in info["overridden_ulps"]), \
         ("an overridden ReLU tie is not within rounding of 0", info)
     return prio.detach(), ex, ref_g, info
+
+
+# ---- TD-update cases with masked actions, distinct targets and Adam state ------
+# (tests/test_gpu_adam.py, test_gpu_learner_masks.py, test_gpu_learner_steps.py)
+
+def adam_ref(p, g, m, v, step, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=10.0,
+             grad_div=None):
+    """clip_grad_norm_ + torch.optim.Adam (non-amsgrad, L2 weight decay, the lerp
+    form) restated in fp64 on the CPU, applied to the inputs upcast.  Returns
+    (p, m, v, norm): the new state and the gradient norm before clipping."""
+    p, g, m, v = (x.detach().cpu().double() for x in (p, g, m, v))
+    if grad_div is not None:
+        g = g / float(grad_div)
+    norm = g.norm()
+    if max_norm > 0:
+        g = g * min(max_norm / (float(norm) + 1e-6), 1.0)
+    if weight_decay != 0:
+        g = g + weight_decay * p
+    m = m + (g - m) * (1 - betas[0])
+    v = v * betas[1] + g * g * (1 - betas[1])
+    bc1, bc2 = 1 - betas[0] ** step, 1 - betas[1] ** step
+    denom = v.sqrt() / (bc2 ** 0.5) + eps
+    return p - (lr / bc1) * (m / denom), m, v, float(norm)
+
+
+def adam_errors(p_gpu, m_gpu, v_gpu, ref, p_before):
+    """(err_m, err_v, err_p, bar_p) of one Adam transition against adam_ref's
+    result: m, v normwise (bar 1e-6: a few fp32 roundings plus the norm
+    reduction's ~1e-7 through the clip coefficient); p absolute against
+    bar_p = 2^-24·max|p_ref| + 1e-5·max|p_ref - p_before| (the final fp32 rounding
+    of p plus the fp32 forward bar on the step itself)."""
+    p_ref, m_ref, v_ref = ref[:3]
+    p_before = p_before.detach().cpu().double()
+    err_p = float((p_gpu.detach().cpu().double() - p_ref).abs().max())
+    bar_p = 2.0 ** -24 * float(p_ref.abs().max()) + 1e-5 * float((p_ref - p_before).abs().max())
+    return normwise(m_gpu, m_ref), normwise(v_gpu, v_ref), err_p, bar_p
+
+
+def masked_avail(B, T1, A, n_actions=5, seed=0, dtype=torch.int32):
+    """avail_actions [B, T1, A, n_actions] from a seeded CPU generator: Bernoulli(0.5)
+    per action with action 0 always available; agent 0 has only action 0 at every
+    step; one (b, t) has every agent down to that single action.  Step T (the
+    last of the T1) is drawn like the rest."""
+    g = torch.Generator().manual_seed(seed)
+    av = (torch.rand(B, T1, A, n_actions, generator=g) < 0.5).to(torch.int32)
+    av[..., 0] = 1
+    av[:, :, 0, 1:] = 0
+    b = int(torch.randint(0, B, (1,), generator=g))
+    t = int(torch.randint(0, T1, (1,), generator=g))
+    av[b, t, :, 1:] = 0
+    return av.to(dtype)
+
+
+def argmax_preconditions(q, avail):
+    """From the oracle's online Q [B, T1, A, nA] and avail: (share of (b, t, a) whose
+    masked argmax differs from the unmasked one, the smallest top-two gap of the
+    masked Q over rows with >= 2 available actions relative to max|Q|)."""
+    q = q.detach().cpu().double()
+    on = avail.cpu() != 0
+    qm = q.masked_fill(~on, -9999999.0)
+    moved = float((qm.argmax(-1) != q.argmax(-1)).double().mean())
+    top2 = qm.topk(2, dim=-1).values
+    rows = on.sum(-1) >= 2
+    gap = float((top2[..., 0] - top2[..., 1])[rows].min() / q.abs().max())
+    return moved, gap
+
+
+def split_flat(flat, pa, pm):
+    """A flat parameter vector (agent then mixer, reference order) as fp64 CPU
+    dicts shaped like pa / pm."""
+    flat = flat.detach().cpu().double()
+    out, off = [], 0
+    for src in (pa, pm):
+        d = {}
+        for k, v in src.items():
+            d[k] = flat[off:off + v.numel()].view_as(v).clone()
+            off += v.numel()
+        out.append(d)
+    assert off == flat.numel()
+    return out

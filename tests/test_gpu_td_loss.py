@@ -88,6 +88,43 @@ def test_td_loss_native_mask_dtypes(tdt, fdt, algo):
     assert torch.equal(out["loss"][1:], ref["loss"][1:])
 
 
+@pytest.mark.parametrize("algo", ["sequential", "wave"])
+def test_td_loss_all_masked_episode(algo):
+    """An episode with filled all zero (Σ_t mask = 0: the reference's priority is 0/0,
+    the kernels give 0) beside one that terminates at step 0 (Σ_t mask = 1) and ragged
+    others: the all-masked episode has priority exactly 0, a dL/dQtot row of exact
+    zeros, finite targets, and adds nothing to Σ mask; everything else matches the
+    oracle at 1e-5."""
+    from t2omca_amd import ops
+    B, T, dead, first = 9, 7, 2, 5
+    qtot, qtgt, reward, term, filled, w = _case(B, T, 77)
+    filled[dead], term[dead] = 0.0, 0.0
+    filled[first], term[first] = 0.0, 0.0
+    filled[first, 0] = term[first, 0] = 1.0
+    tg, gq, prio, loss, msum = _ref(qtot.double(), qtgt.double(), reward.double(), term.double(),
+                                    filled.double(), w.double(), 0.99, 0.6)
+    live = torch.arange(B) != dead
+    assert torch.isnan(prio[dead]) and torch.isfinite(prio[live]).all()
+    c = lambda t: t.cuda().contiguous()  # noqa: E731
+    acc = torch.zeros(1, device="cuda")
+    out = ops.td_loss(c(qtot), c(qtgt), c(reward), c(term), c(filled), c(w), gamma=0.99, td_lambda=0.6,
+                      mask_sum=0.0, algo=algo, mask_sum_acc=acc)
+    o = {k: out[k].cpu().double() for k in ("gq", "targets", "prio", "loss")}
+    assert float(o["prio"][dead]) == 0.0
+    assert torch.equal(o["gq"][dead], torch.zeros(T, dtype=torch.float64))
+    assert torch.isfinite(o["targets"]).all() and torch.isfinite(o["gq"]).all()
+    # Σ mask without the all-masked episode's share (an integer: exact)
+    live_mask = filled[live].clone()
+    live_mask[:, 1:] *= 1 - term[live][:, :-1]
+    assert float(o["loss"][1]) == float(live_mask.sum()) == float(msum) == float(acc)
+    assert _nw(o["targets"][live], tg[live]) < 1e-5
+    assert _nw(o["gq"][live], gq[live]) < 1e-5
+    assert _nw(o["prio"][live], prio[live]) < 1e-5
+    assert abs(float(o["loss"][0]) - float(loss)) <= 1e-5 * max(1.0, abs(float(loss)))
+    # the episode that ends at step 0: one masked step, its target the reward alone
+    assert _nw(o["targets"][first, :1], reward[first, :1].double()) < 1e-6
+
+
 def test_td_loss_wave_scan_long_horizon():
     """The wave scan takes any T (no LDS staging): T = 6000 is past the sequential
     kernel's LDS limit (T2O_EUNSUPPORTED there)."""
