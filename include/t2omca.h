@@ -17,6 +17,8 @@
  *   t2o_mixer_unroll_bwd   BPTT of the above
  *   t2o_td_loss            learner.train's TD target / loss / priorities
  *                          (call site per_run.py:224-238; PyMARL2 contract)
+ *   t2o_td_stats           the masked sums the learner's log values come from
+ *   t2o_episode_stats      the runner's per-run statistics (parallel_runner.py:202-210)
  *   t2o_adam_step          optimiser step with global-norm clipping
  *   t2o_env_step / reset   MultiAgvOffloadingEnv.step/reset/get_obs/get_state
  *                          (environment_multi_mec.py:184-366, normalization.py)
@@ -163,6 +165,7 @@ int t2o_unpack_grads(const t2o_layout* L, const float* params, const float* gpac
 #define T2O_ARGS_MIXER_BWD 3
 #define T2O_ARGS_TAPE 4
 #define T2O_ARGS_TD 5
+#define T2O_ARGS_TD_STATS 6
 int t2o_args_sizeof(int which); /* sizeof the T2O_ARGS_* struct, -1 for an unknown one */
 
 /* Agent unroll forward (TransformerAgent.forward over t, transf_agent.py:54-76) for
@@ -395,6 +398,43 @@ typedef struct {
   int32_t B, T;
 } t2o_td_args;
 int t2o_td_loss(const t2o_td_args* a, void* stream);
+
+/* ---- logged statistics (t2o_stats.hip).  Both entry points run one workgroup,
+ * accumulate in fp64 without atomics and combine their partial sums in a fixed
+ * tree, so a result depends on the inputs and the element count only: it is
+ * bit-identical run to run and on any device.  T2O_EINVAL (a null required
+ * pointer, a size < 1) is returned before any launch. */
+
+/* The masked sums a PyMARL2 NQLearner logs from, over the TD loss's mask
+ * m[b][t] = filled[t] * (t > 0 ? 1 - term[t-1] : 1): out = { Σ m, Σ |qtot - targets| m,
+ * Σ qtot m, Σ targets m } (overwritten; every operand converted to fp64 first).
+ * td_error_abs = out[1] / out[0]; q_taken_mean = out[2] / (out[0] * n_agents);
+ * target_mean = out[3] / (out[0] * n_agents). */
+typedef struct {
+  const float* qtot;          /* [B][T] online mixer (t2o_td_args.qtot) */
+  const float* targets;       /* [B][T] (t2o_td_args.targets) */
+  const void* term;           /* as t2o_td_args: [b][t] 0/1 (NULL: none), strides tm_* */
+  int64_t tm_sb, tm_st;
+  const void* filled;         /* as t2o_td_args: [b][t] 0/1 (NULL: all), strides fl_* */
+  int64_t fl_sb, fl_st;
+  int32_t term_dtype, filled_dtype;  /* T2O_DT_* */
+  int32_t B, T;
+  double* out;                /* out [4] */
+} t2o_td_stats_args;
+int t2o_td_stats(const t2o_td_stats_args* a, void* stream);
+
+/* The runner's statistics of one finished run of n envs (parallel_runner.py:202-210),
+ * added to acc:
+ *   acc[0] += n; acc[1] += Σ returns[i];
+ *   over the envs with terminated[i] != 0 (their info dicts, :169-170):
+ *   acc[2] += reward[i]; acc[3..6] += info[i][0..3] (delay_reward, overtime_penalty,
+ *   channel_utilization_rate, conflict_ratio); acc[7] += 1 (episode_limit);
+ *   acc[8..9] += info[i][4..5] (task_completion_rate, task_completion_delay).
+ * reward / terminated / info are t2o_env_run's outputs after the run's last step
+ * (info [n][6]); an unterminated env's row (NaN task_completion_*) is never read. */
+#define T2O_EP_STATS 10
+int t2o_episode_stats(const double* reward, const double* info, const uint8_t* terminated, const double* returns,
+                      int64_t n, double* acc, void* stream);
 
 /* clip_grad_norm_(max_grad_norm) + Adam (torch.optim.Adam semantics, L2
  * weight decay) over n floats.  workspace: t2o_adam_workspace_floats() floats

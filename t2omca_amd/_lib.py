@@ -77,7 +77,10 @@ TapeArgs = _args_class("TapeArgs", 4, "L:L, pack:P, tape:P, tiles:J, gslabs:P, n
 TDArgs = _args_class("TDArgs", 5, """qtot:P, qtot_tgt:P, reward:P, rw_sb:J, rw_st:J, term:P, tm_sb:J, tm_st:J,
     filled:P, fl_sb:J, fl_st:J, per_weight:P, gq:P, targets:P, prio:P, loss:P, mask_sum_acc:P, gamma:F,
     td_lambda:F, mask_sum:F, term_dtype:I, filled_dtype:I, algo:I, B:I, T:I""")
-ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs)
+TDStatsArgs = _args_class("TDStatsArgs", 6, """qtot:P, targets:P, term:P, tm_sb:J, tm_st:J, filled:P, fl_sb:J,
+    fl_st:J, term_dtype:I, filled_dtype:I, B:I, T:I, out:P""")
+ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs)
+EP_STATS = 10  # include/t2omca.h T2O_EP_STATS
 
 
 # mixer head positivity functions (include/t2omca.h T2O_POS_*; n_transf_mixer.py:95-103)
@@ -113,6 +116,8 @@ EXPORTS = {
     "t2o_agent_bwd_tape_format": (ctypes.c_int, [ctypes.POINTER(Layout), ctypes.c_int]),
     "t2o_agent_bwd_ranges": (ctypes.c_int, [ctypes.POINTER(Layout), ctypes.c_int]),
     "t2o_td_loss": (ctypes.c_int, [ctypes.POINTER(TDArgs), ctypes.c_void_p]),
+    "t2o_td_stats": (ctypes.c_int, [ctypes.POINTER(TDStatsArgs), ctypes.c_void_p]),
+    "t2o_episode_stats": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "t2o_args_sizeof": (ctypes.c_int, [ctypes.c_int]),
     "t2o_abi_version": (ctypes.c_int, []),
     "t2o_adam_step": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_double] * 3 +
@@ -148,6 +153,11 @@ EXPORTS = {
 _DIAGNOSTIC = {"t2o_bf_swz", "t2o_probe_lane_ops", "t2o_probe_scatter_ops", "t2o_probe_posf", "t2o_probe_xdl_hazards",
                "t2o_layout_instance",
                "t2o_abi_version"}
+# the logged statistics (same ABI version: nothing existing moved), which a build
+# from before them lacks; calling one on such a library raises AttributeError
+_OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats"}
+# argument structs of optional exports: no size to check where the export is absent
+_STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats"}
 
 _lib = None
 
@@ -163,8 +173,8 @@ def lib():
                                "(there is no CPU fallback)")
         h = ctypes.CDLL(path)
         for name, (res, args) in EXPORTS.items():
-            if name in _DIAGNOSTIC and path != LIB and not hasattr(h, name):
-                continue  # an older build under A/B (T2O_LIB) may lack a diagnostic export
+            if name in _OPTIONAL and path != LIB and not hasattr(h, name):
+                continue  # an older build under A/B (T2O_LIB) may lack these exports
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args
@@ -172,6 +182,8 @@ def lib():
             raise RuntimeError(f"t2omca_amd: {path} has C-ABI version {h.t2o_abi_version()}, this binding "
                                f"mirrors include/t2omca.h version {ABI_VERSION}; rebuild the library")
         for cls in ARGS_STRUCTS:  # the mirrors of the argument structs must match the library's
+            if cls in _STRUCT_EXPORT and not hasattr(h, _STRUCT_EXPORT[cls]):
+                continue
             if h.t2o_args_sizeof(cls.WHICH) != ctypes.sizeof(cls):
                 raise RuntimeError(f"t2omca_amd: {cls.__name__} is {ctypes.sizeof(cls)} bytes here, "
                                    f"{h.t2o_args_sizeof(cls.WHICH)} in {path}; rebuild the library")

@@ -56,7 +56,8 @@ class TDLearner:
     def __init__(self, agent, mixer, *, lr=1e-3, gamma=0.99, td_lambda=0.6, grad_norm_clip=10.0,
                  target_update_interval=200, optim_betas=(0.9, 0.999), optim_eps=1e-8, weight_decay=0.0,
                  detach_mixer_hidden=False, process_group=None, priorities_to_cpu=True, precision="fp32",
-                 overlap=True, td_algo="auto", contract="side", pipeline="auto", pipeline_ranges=6):
+                 overlap=True, td_algo="auto", contract="side", pipeline="auto", pipeline_ranges=6,
+                 logger=None, learner_log_interval=10000):
         # options first (a bad value fails here, not inside the first train())
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
@@ -124,6 +125,12 @@ class TDLearner:
         self.pack_mt = torch.empty_like(self.pack_m)
         self._pack_targets()
         self._slabs = {}
+        # logged statistics (PyMARL2 NQLearner: every learner_log_interval env steps);
+        # without a logger train() issues nothing for them
+        self.logger = logger
+        self.learner_log_interval = learner_log_interval
+        self.log_stats_t = -learner_log_interval - 1
+        self._stat = torch.zeros(6, dtype=torch.float64, device=dev) if logger is not None else None
 
     # -- parameters --------------------------------------------------------
     def _params_written(self):
@@ -389,7 +396,8 @@ class TDLearner:
             work_a = allreduce_async(self.grad[:self.na], self.pg)
             main.wait_stream(side)
             wait_all((work_m_, work_a))
-            return self._finish(episode_num, td, {"y": o_on["y"].clone()})  # (o_on: reused buffers)
+            # (o_on: reused buffers)
+            return self._finish(episode_num, td, {"y": o_on["y"].clone()}, t_env, term, filled)
         contract_m, gqv, ghid, _ = ops.mixer_unroll_bwd(self.sm, self.pack_m, state, h_on, o_on, td["gq"],
                                                         slabs=slabs_m, timer=self.timer, tape=tape_m,
                                                         defer_contract=True, work=work_m)
@@ -418,15 +426,38 @@ class TDLearner:
             work_a = allreduce_async(self.grad[:self.na], self.pg)
             main.wait_stream(side)
             wait_all((work_m, work_a))
-        return self._finish(episode_num, td, o_on)
+        return self._finish(episode_num, td, o_on, t_env, term, filled)
 
-    def _finish(self, episode_num, td, o_on):
+    def _log_stats(self, t_env, td, qtot, term, filled):
+        """The NQLearner log values, when one is due: one library launch (the masked
+        fp64 sums of |td|, Qtot and the targets, t2o_td_stats) beside two small copies
+        that gather the loss, Σ mask and the gradient norm, with a process group one
+        all-reduce (the sums become the global ones), then ONE host read of seven
+        doubles."""
+        st = self._stat
+        st[:2].copy_(td["loss"])  # Σ_b w_b Σ_t ½ td² m (un-normalised), local Σ mask
+        ops.td_stats(qtot, td["targets"], term, filled, out=st[2:])
+        if self._world() > 1:
+            dist.all_reduce(st, op=dist.ReduceOp.SUM, group=self.pg)
+        loss_sum, mask_sum, m, abs_sum, q_sum, tgt_sum, grad_norm = torch.cat([st, self.grad_norm.double()]).tolist()
+        n_agents = self.sm.agents
+        log = self.logger.log_stat
+        log("loss_td", loss_sum / mask_sum, t_env)
+        log("grad_norm", grad_norm, t_env)
+        log("td_error_abs", abs_sum / m, t_env)
+        log("q_taken_mean", q_sum / (m * n_agents), t_env)
+        log("target_mean", tgt_sum / (m * n_agents), t_env)
+        self.log_stats_t = t_env
+
+    def _finish(self, episode_num, td, o_on, t_env=0, term=None, filled=None):
         # 7. clip + Adam
         self.step_count += 1
         ops.adam_step(self.params, self.grad[:-1], self.exp_avg, self.exp_avg_sq, self.step_count, lr=self.lr,
                       betas=self.betas, eps=self.eps, weight_decay=self.wd, max_grad_norm=self.clip,
                       workspace=self.adam_ws, grad_div=self.grad[-1:], grad_norm_out=self.grad_norm)
         self._params_written()
+        if self.logger is not None and t_env - self.log_stats_t >= self.learner_log_interval:
+            self._log_stats(t_env, td, o_on["y"], term, filled)
         if (episode_num - self.last_target_update_episode) / self.target_update_interval >= 1.0:
             self.update_targets()
             self.last_target_update_episode = episode_num

@@ -573,3 +573,44 @@ def obs_expand(wire, snap_n, snap, out=None, out64=None):
                                out.stride(0), out.stride(1), ptr(out64), B, T1, A, stream_ptr(wire.device)),
           "obs_expand")
     return out
+
+
+def td_stats(qtot, targets, terminated=None, filled=None, out=None):
+    """The masked sums the learner logs from (include/t2omca.h t2o_td_stats): qtot /
+    targets f32 [B,T] dense, terminated / filled [B, >=T] views as td_loss takes
+    them (read in place; None: none terminated / all filled).  Returns `out`, f64
+    [4] = [Σm, Σ|q-tgt|m, Σq·m, Σtgt·m] (overwritten), summed in fp64 in an order
+    fixed by (B, T).  One launch, no host read."""
+    _dev(qtot, targets)
+    for m in (terminated, filled):
+        if m is not None and not m.is_cuda:
+            raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    B, T = qtot.shape
+    assert qtot.is_contiguous() and targets.is_contiguous() and targets.shape == qtot.shape
+    if out is None:
+        out = torch.empty(4, dtype=torch.float64, device=qtot.device)
+    assert out.dtype == torch.float64 and out.numel() == 4 and out.is_contiguous() and out.is_cuda
+    ts, fs = _mstrides(terminated), _mstrides(filled)
+    a = _lib.TDStatsArgs(qtot=_p(qtot), targets=_p(targets), term=_p(terminated), tm_sb=ts[0], tm_st=ts[1],
+                         filled=_p(filled), fl_sb=fs[0], fl_st=fs[1], term_dtype=_mask_dtype(terminated),
+                         filled_dtype=_mask_dtype(filled), B=B, T=T, out=_p(out))
+    check(lib().t2o_td_stats(ctypes.byref(a), stream_ptr(qtot.device)), "td_stats")
+    return out
+
+
+def episode_stats(reward, info, terminated, returns, acc):
+    """acc += the runner's statistics of one finished run (include/t2omca.h
+    t2o_episode_stats): reward f64 [n], info f64 [n, 6] (env.INFO_KEYS columns),
+    terminated uint8 [n], returns f64 [n], acc f64 [EP_STATS], all dense on the
+    device.  One launch, no host read."""
+    n = returns.numel()
+    for t, dt, shape in ((reward, torch.float64, (n,)), (info, torch.float64, (n, 6)),
+                         (terminated, torch.uint8, (n,)), (returns, torch.float64, (n,)),
+                         (acc, torch.float64, (_lib.EP_STATS,))):
+        if not t.is_cuda:
+            raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise TypeError(f"episode_stats: expected a dense {shape} {dt} tensor, got {tuple(t.shape)} {t.dtype}")
+    check(lib().t2o_episode_stats(ptr(reward), ptr(info), ptr(terminated), ptr(returns), n, ptr(acc),
+                                  stream_ptr(acc.device)), "episode_stats")
+    return acc

@@ -32,14 +32,29 @@ batch carries the observation wire format instead of the dense obs —
 ``obs_nrm_n`` [n] / ``obs_nrm`` [n, 2, 9A] — and each step's dense obs goes only
 to a one-step scratch buffer the agent reads.  ``ops.obs_expand`` (called by
 TDLearner.train when the batch has no ``obs``) rebuilds the dense obs exactly.
+
+Statistics (parallel_runner.py:193-231; off by default): with a ``logger`` (or
+``collect_stats=True``) every run ends with ONE more launch, ``ops.episode_stats``,
+which adds the run's returns and the terminated envs' info values to a device
+accumulator of its mode (train / test) — no host read.  When the reference's
+schedule (:212-219) says a log is due, ``_log`` reads that accumulator once,
+logs the means under the reference's keys and clears it.
 """
 import dataclasses
 
 import torch
+import torch.distributed as dist
 
 from . import ops
-from .distributed import rank as dist_rank, rank_seed
+from ._lib import EP_STATS
+from .distributed import rank as dist_rank, rank_seed, world_size
+from .env import INFO_KEYS
 from .episode_batch import DeviceEpisodeBatch
+
+# what accumulator slots 2.. sum (include/t2omca.h t2o_episode_stats): the keys of the
+# terminated step's info dict (environment_multi_mec.py:340-363), logged as key + "_mean"
+STAT_KEYS = ("reward",) + INFO_KEYS[:4] + ("episode_limit",) + INFO_KEYS[4:]
+assert len(STAT_KEYS) == EP_STATS - 2
 
 
 class LinearSchedule:
@@ -55,8 +70,20 @@ class LinearSchedule:
 
 class RolloutRunner:
     def __init__(self, agent, env, *, epsilon_start=1.0, epsilon_finish=0.05, epsilon_anneal_time=50000,
-                 seed=None, compact_obs=False, precision="fp32"):
-        """precision: the agent step's MFMA operands — "fp32" (the reference's
+                 seed=None, compact_obs=False, precision="fp32", logger=None, test_nepisode=None,
+                 runner_log_interval=2000, collect_stats=None, process_group=None):
+        """logger: an object with ``log_stat(key, value, t)`` (statlog.StatsLogger); with
+        one, or with collect_stats=True, the runner keeps the reference's run statistics
+        (module docstring) and logs them on its schedule: test statistics once
+        max(1, test_nepisode // n) test runs are accumulated (test_nepisode None: one
+        run), otherwise every runner_log_interval env steps.  process_group: the means
+        logged are those over every rank's episodes (one SUM all-reduce of the
+        accumulator before it is read); every rank must then run the same number of
+        envs and the same episode limit, and call run() / train_stats / test_stats in
+        the same order, since whether a log is due is decided from host counters that
+        are equal only then.
+
+        precision: the agent step's MFMA operands — "fp32" (the reference's
         precision, default) or "bf16" (bf16 weight / activation operands, fp32
         accumulation, LayerNorm, softmax and recurrent state, as the learner's bf16
         mode; greedy actions can differ from fp32's where two Q values are within
@@ -89,6 +116,18 @@ class RolloutRunner:
         # (agent step, action selection, env step) on every timer_every-th timestep
         self.timer = None
         self.timer_every = 10
+        # statistics (parallel_runner.py:48-55, 193-231)
+        self.logger = logger
+        self.collect_stats = bool(collect_stats) or logger is not None
+        self.batch_size = self.n
+        self.test_nepisode = self.n if test_nepisode is None else int(test_nepisode)
+        self.runner_log_interval = runner_log_interval
+        self.log_train_stats_t = -100000
+        self.pg = process_group
+        self._acc = None  # [2][EP_STATS] fp64 on the device: train, test
+        self._n_acc = [0, 0]  # episodes in each accumulator (host: the schedule never synchronises)
+        if self.collect_stats:
+            self._acc = torch.zeros(2, EP_STATS, dtype=torch.float64, device=self.device)
 
     # -- replay batch ---------------------------------------------------------
     def _alloc(self):
@@ -148,7 +187,71 @@ class RolloutRunner:
             batch["obs_nrm_n"] = env.snap_n.clone()
             batch["obs_nrm"] = env.snap.clone()
         self.last_returns = ret
+        if self.collect_stats:
+            self._run_stats(bool(test_mode), ret, eps)
         return DeviceEpisodeBatch(batch)
+
+    # -- statistics -----------------------------------------------------------------
+    def _run_stats(self, test_mode, ret, eps):
+        """The end of ParallelRunner.run (:202-219): this run into its mode's
+        accumulator (one launch), then the log schedule."""
+        env = self.env
+        ops.episode_stats(env.reward, env.info, env.terminated, ret, self._acc[int(test_mode)])
+        self._n_acc[int(test_mode)] += self.n
+        if self.logger is None:
+            return
+        n_test_runs = max(1, self.test_nepisode // self.n) * self.n
+        if test_mode and self._n_acc[1] == n_test_runs:
+            self._log(test_mode)
+        elif self.t_env - self.log_train_stats_t >= self.runner_log_interval:
+            self._log(test_mode)
+            self.logger.log_stat("epsilon", eps, self.t_env)
+            self.log_train_stats_t = self.t_env
+
+    def _sums(self, mode):
+        """The accumulator of a mode on the host (over every rank with a process
+        group): the one synchronising read of the statistics."""
+        acc = self._acc[int(mode)]
+        if world_size(self.pg) > 1:
+            acc = acc.clone()
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=self.pg)
+        return acc.tolist()
+
+    def _log(self, test_mode):
+        """ParallelRunner._log (:223-231)."""
+        prefix = "test_" if test_mode else ""
+        s = self._sums(test_mode)
+        self.logger.log_stat(prefix + "return_mean", s[1] / s[0], self.t_env)
+        for i, k in enumerate(STAT_KEYS):
+            self.logger.log_stat(prefix + k + "_mean", s[2 + i] / s[0], self.t_env)
+        self._acc[int(test_mode)].zero_()
+        self._n_acc[int(test_mode)] = 0
+
+    def _stats_dict(self, mode):
+        if self._acc is None:
+            raise RuntimeError("this runner collects no statistics (give it a logger or collect_stats=True)")
+        s = self._sums(mode)
+        return {"n_episodes": int(s[0]), "return": s[1], **{k: s[2 + i] for i, k in enumerate(STAT_KEYS)}}
+
+    @property
+    def train_stats(self):
+        """The sums accumulated over the train runs since the last log, as the
+        reference's train_stats dict plus "return" (Σ episode returns).  A
+        synchronising read, for inspection (a collective with a process group)."""
+        return self._stats_dict(False)
+
+    @property
+    def test_stats(self):
+        """As train_stats, for the test runs."""
+        return self._stats_dict(True)
+
+    def evaluate(self, n_runs=None, new_buffers=True):
+        """max(1, test_nepisode // n) greedy runs (per_run.py:240,255-256), after which
+        the test statistics are logged; returns the last run's batch."""
+        batch = None
+        for _ in range(max(1, self.test_nepisode // self.n) if n_runs is None else int(n_runs)):
+            batch = self.run(test_mode=True, new_buffers=new_buffers)
+        return batch
 
     def _dest(self, tm, t):
         if self.compact_obs:
