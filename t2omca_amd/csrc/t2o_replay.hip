@@ -85,17 +85,91 @@ __global__ __launch_bounds__(PER_THREADS) void per_sample_kernel(const float* __
   }
 }
 
-__global__ void per_update_kernel(float* __restrict__ p, const int64_t* __restrict__ idx,
-                                  const float* __restrict__ prio, int64_t n, float alpha, float eps,
-                                  float* __restrict__ max_prio) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const float v = prio[k] + eps;
-  // PyMARL2 asserts priority > 0; a non-positive or non-finite value (a NaN's bit
-  // pattern would win the unsigned max below for good) leaves the episode as it was
-  if (!(v > 0.f) || !isfinite(v)) return;
-  p[idx[k]] = powf(v, alpha);
-  atomicMax(reinterpret_cast<unsigned int*>(max_prio), __float_as_uint(v));  // v > 0: bit order = value order
+constexpr int UPD_THREADS = 256;
+constexpr int UPD_WAVE_ENTRIES = 4;                                     // entries one wave decides
+constexpr int UPD_BLOCK_ENTRIES = UPD_THREADS / 64 * UPD_WAVE_ENTRIES;  // 16 consecutive entries per workgroup
+constexpr int UPD_TILE = 1024;                                          // later keys staged in LDS at a time
+constexpr int64_t UPD_NO_SLOT = -1;                                     // the key of an entry that writes nothing
+
+// PyMARL2 asserts priority > 0; a non-positive or non-finite value (a NaN's bit
+// pattern would win the unsigned max below for good) leaves the episode as it was.
+__device__ __forceinline__ bool per_update_valid(float v) { return (v > 0.f) && isfinite(v); }
+
+// slot if the entry writes, UPD_NO_SLOT (all ones) if not — as arithmetic on the
+// loaded slot: a select would let the compiler put the load behind a branch, and
+// the loads of a thread would then wait for each other
+__device__ __forceinline__ int64_t per_update_key(int64_t slot, bool writes) { return slot | -(int64_t)!writes; }
+
+// PyMARL2 updates priorities in a sequential loop, so of several entries naming
+// one slot the last valid one stays (oracle/ref_replay.update).  Entry k writes
+// p[idx[k]] only if no valid entry after it names the same slot.  A workgroup
+// takes 16 consecutive entries; it stages the keys (slot, or none for an invalid
+// priority) of the entries after its first one in LDS, a tile of 1024 at a time
+// (one tile at the driver's n <= 1024: every load of a thread is in flight at
+// once), and each wave compares its 4 entries against the tile, a lane per key.
+// Each slot so has at most one writer in the whole grid: the result is ordered
+// by construction — nothing depends on which wave runs first, which no test
+// could show — at n^2 / 2 key compares (cost in DESIGN.md §5).  The max takes
+// every valid entry, overwritten ones included, as the sequential loop does.
+__global__ __launch_bounds__(UPD_THREADS) void per_update_kernel(float* __restrict__ p,
+                                                                 const int64_t* __restrict__ idx,
+                                                                 const float* __restrict__ prio, int64_t n,
+                                                                 float alpha, float eps,
+                                                                 float* __restrict__ max_prio) {
+  __shared__ int64_t key[UPD_TILE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t k0 = (int64_t)blockIdx.x * UPD_BLOCK_ENTRIES;  // < n by the grid size
+  const int64_t kw = k0 + (tid >> 6) * UPD_WAVE_ENTRIES;       // this wave's first entry
+  // the max, a thread per entry in the first n / 256 workgroups: atomics on one word
+  // serialise, and this way a wave issues one for its 64 entries, not one per entry
+  const int64_t km = (int64_t)blockIdx.x * UPD_THREADS + tid;
+  const float vm = prio[km < n ? km : n - 1] + eps;  // loaded with the entries below: one wait for all
+  float v[UPD_WAVE_ENTRIES];
+  int64_t slot[UPD_WAVE_ENTRIES];
+  bool later[UPD_WAVE_ENTRIES];  // a later valid entry names this slot
+#pragma unroll
+  for (int e = 0; e < UPD_WAVE_ENTRIES; ++e) {
+    const int64_t k = kw + e, kc = k < n ? k : n - 1;  // clamped: no load waits for a branch
+    v[e] = prio[kc] + eps;
+    slot[e] = per_update_key(idx[kc], k < n && per_update_valid(v[e]));
+    later[e] = false;
+  }
+  if (km < n && per_update_valid(vm))
+    atomicMax(reinterpret_cast<unsigned int*>(max_prio), __float_as_uint(vm));  // v > 0: bit order = value order
+  for (int64_t base = k0 + 1; base < n; base += UPD_TILE) {  // workgroup-uniform trip count
+    __syncthreads();
+    int64_t sj[UPD_TILE / UPD_THREADS];
+    float vj[UPD_TILE / UPD_THREADS];
+#pragma unroll
+    for (int u = 0; u < UPD_TILE / UPD_THREADS; ++u) {  // every load of the tile in flight at once
+      const int64_t j = base + u * UPD_THREADS + tid, jc = j < n ? j : n - 1;
+      sj[u] = idx[jc];
+      vj[u] = prio[jc];
+    }
+#pragma unroll
+    for (int u = 0; u < UPD_TILE / UPD_THREADS; ++u)
+      key[u * UPD_THREADS + tid] =
+          per_update_key(sj[u], base + u * UPD_THREADS + tid < n && per_update_valid(vj[u] + eps));
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < UPD_TILE / 64; ++u) {
+      const int64_t s = key[u * 64 + lane], j = base + u * 64 + lane;
+#pragma unroll
+      for (int e = 0; e < UPD_WAVE_ENTRIES; ++e) later[e] |= (s == slot[e]) & (j > kw + e);
+    }
+  }
+  // lane e takes entry e of its wave, so that one powf serves the four
+  float v_mine = 0.f;
+  int64_t slot_mine = UPD_NO_SLOT;
+#pragma unroll
+  for (int e = 0; e < UPD_WAVE_ENTRIES; ++e) {
+    const bool overwritten = __any(later[e]);  // every lane of the wave is here
+    if (lane == e && !overwritten) {
+      v_mine = v[e];
+      slot_mine = slot[e];
+    }
+  }
+  if (slot_mine != UPD_NO_SLOT) p[slot_mine] = powf(v_mine, alpha);
 }
 
 // dst[k] = src[idx[k]] for rows of row_units units of U bytes
@@ -128,8 +202,9 @@ extern "C" int t2o_per_update(float* p, const int64_t* idx, const float* prio, i
                               float* max_prio, void* stream) {
   if (!p || !idx || !prio || !max_prio || n < 0) return T2O_EINVAL;
   if (n == 0) return 0;
-  hipLaunchKernelGGL(per_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, idx,
-                     prio, n, alpha, eps, max_prio);
+  const unsigned blocks = (unsigned)((n + UPD_BLOCK_ENTRIES - 1) / UPD_BLOCK_ENTRIES);
+  hipLaunchKernelGGL(per_update_kernel, dim3(blocks), dim3(UPD_THREADS), 0, (hipStream_t)stream, p, idx, prio, n, alpha,
+                     eps, max_prio);
   return (int)hipGetLastError();
 }
 
