@@ -31,6 +31,11 @@ import torch
 from . import env_spec as S
 from .distributed import rank as dist_rank, rank_seed
 from ._lib import check, lib, stream_ptr
+from .state import check_fields, copy_checked
+
+# the env kernel's state[17], in the header's order and under its names (include/t2omca.h)
+STATE_KEYS = ("mec_index", "x", "y", "q_size", "q_thr", "q_head", "q_len", "task_num", "task_success",
+              "remain_delay", "last_ack", "time_slot", "draw", "nrm_n", "nrm_mean", "nrm_S", "nrm_std")
 
 INFO_KEYS = ("delay_reward", "overtime_penalty", "channel_utilization_rate", "conflict_ratio",
              "task_completion_rate", "task_completion_delay")
@@ -176,6 +181,30 @@ class VecEnv:
         d = self._dest(dest)
         info = {k: self.info[:, i] for i, k in enumerate(INFO_KEYS)}
         return self.reward, self.terminated.bool(), info, d["state"], d["avail"], d["obs"]
+
+    # -- saved state (driver.save_run_state) ---------------------------------------------
+    def _geometry(self):
+        return {"n_envs": self.n_envs, "A": self.A, "M": self.M, "C": self.C, "T": self.T, "qmax": self.qmax,
+                "obs_entity_mode": self.obs_entity_mode, "spec": [float(v) for v in self._spec]}
+
+    def state_dict(self):
+        """Everything the next reset / step reads: the 17 state tensors under the
+        header's names (include/t2omca.h) as CPU copies — positions, queues, draw
+        counters and the running observation normaliser — and the seed in use
+        (already mixed with the rank).  The output tensors (obs, reward, info, the
+        wire snapshot, ...) are not state: the next reset rewrites them.  The copies
+        are ordered after the launches queued on the current stream."""
+        sd = {"format": 1, "seed": self.seed, **self._geometry()}
+        sd["state"] = {k: t.detach().cpu() for k, t in zip(STATE_KEYS, self._state)}
+        return sd
+
+    def load_state_dict(self, sd):
+        """In place, into the existing device tensors.  ValueError naming the field
+        when the saved env has another geometry, obs mode or env_spec constants."""
+        check_fields("VecEnv", sd, {"format": 1, **self._geometry()})
+        for k, t in zip(STATE_KEYS, self._state):
+            copy_checked("VecEnv", k, t, sd["state"][k])
+        self.seed = int(sd["seed"])
 
     # -- state views (tests / diagnostics) ----------------------------------------------
     @property

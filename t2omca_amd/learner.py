@@ -36,6 +36,7 @@ import torch.distributed as dist
 
 from . import ops
 from .distributed import allreduce_async, broadcast_state, wait_all
+from .state import check_fields, copy_checked
 
 
 def _bind_flat(modules, device):
@@ -241,6 +242,34 @@ class TDLearner:
         if len(steps) > 1:
             raise ValueError(f"opt.th: parameters carry different Adam step counts {sorted(steps)}")
         self.step_count = steps.pop() if steps else 0
+        self._sync_replicas()
+
+    # -- saved state (driver.save_run_state) -------------------------------------
+    def state_dict(self):
+        """The whole learner, unlike save_models' PyMARL files: the flat parameters,
+        the target parameters (agent AND mixer half), the Adam moments and step
+        count, and the two schedule counters (target update, log).  CPU copies,
+        ordered after the update queued on the current stream (train() ends with
+        the main stream waiting for the side stream)."""
+        return {"format": 1, "na": self.na, "nm": self.nm, "precision": self.precision,
+                "params": self.params.detach().cpu(), "target_params": self.target_params.detach().cpu(),
+                "exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu(),
+                "step_count": int(self.step_count),
+                "last_target_update_episode": int(self.last_target_update_episode),
+                "log_stats_t": int(self.log_stats_t)}
+
+    def load_state_dict(self, sd):
+        """In place into the flat buffers, which the modules' parameters view; then
+        _sync_replicas: the modules' pack caches dropped, the targets re-packed and
+        data-parallel ranks aligned (a collective with a process group).  ValueError
+        naming the field when the parameter counts or the precision differ."""
+        check_fields("TDLearner", sd, {"format": 1, "na": self.na, "nm": self.nm, "precision": self.precision})
+        with torch.no_grad():
+            for name in ("params", "target_params", "exp_avg", "exp_avg_sq"):
+                copy_checked("TDLearner", name, getattr(self, name), sd[name])
+        self.step_count = int(sd["step_count"])
+        self.last_target_update_episode = int(sd["last_target_update_episode"])
+        self.log_stats_t = int(sd["log_stats_t"])
         self._sync_replicas()
 
     def _sync_replicas(self):

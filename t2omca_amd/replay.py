@@ -24,6 +24,7 @@ import torch
 from ._lib import check, lib, ptr, stream_ptr
 from .episode_batch import DeviceEpisodeBatch, as_tensor_dict
 from .distributed import rank as dist_rank, rank_seed
+from .state import check_fields, copy_checked
 
 
 class PrioritizedReplayBuffer:
@@ -106,6 +107,47 @@ class PrioritizedReplayBuffer:
         per_run.py:228-232 (max_t_filled, [:, :t] slicing, device, to)."""
         idx, w = self.sample_indices(batch_size, t)
         return DeviceEpisodeBatch(self.gather(idx)), idx, w
+
+    # -- saved state (driver.save_run_state) -------------------------------------------
+    def _scheme(self):
+        return {k: [list(v.shape[1:]), str(v.dtype)] for k, v in self.data.items()}
+
+    def state_dict(self, include_data=True):
+        """The ring index, the episode count, the draw counter, the seed in use and the
+        PER constants and ``max_priority``; with include_data also every slab and ``p``
+        (CPU copies: the whole replay).  A state saved with include_data=False loads as
+        an EMPTY buffer that keeps seed / draws — the run goes on, but not bit for bit
+        as the uninterrupted one would: it has to refill before it can be sampled."""
+        sd = {"format": 1, "buffer_size": self.buffer_size, "max_seq_length": self.max_seq_length,
+              "scheme": self._scheme(), "include_data": bool(include_data),
+              "buffer_index": self.buffer_index, "episodes_in_buffer": self.episodes_in_buffer,
+              "draws": self._draws, "seed": self.seed, "alpha": self.alpha, "beta_original": self.beta_original,
+              "beta": self.beta, "beta_increment": self.beta_increment,
+              "max_priority": self.max_priority.detach().cpu()}
+        if include_data:
+            sd["data"] = {k: v.detach().cpu() for k, v in self.data.items()}
+            sd["p"] = self.p.detach().cpu()
+        return sd
+
+    def load_state_dict(self, sd):
+        """In place into the slabs.  ValueError naming the field when the capacity,
+        max_seq_length or the scheme (keys, per-episode shapes, dtypes) differ."""
+        check_fields("PrioritizedReplayBuffer", sd, {"format": 1, "buffer_size": self.buffer_size,
+                                                     "max_seq_length": self.max_seq_length,
+                                                     "scheme": self._scheme()})
+        self._draws, self.seed = int(sd["draws"]), int(sd["seed"])
+        self.alpha, self.beta_original = float(sd["alpha"]), float(sd["beta_original"])
+        self.beta_increment = float(sd["beta_increment"])
+        self.beta = float(sd["beta"])  # (the last sample's; the next sample recomputes it from t)
+        copy_checked("PrioritizedReplayBuffer", "max_priority", self.max_priority, sd["max_priority"])
+        if sd["include_data"]:
+            for k, v in self.data.items():
+                copy_checked("PrioritizedReplayBuffer", f"data[{k!r}]", v, sd["data"][k])
+            copy_checked("PrioritizedReplayBuffer", "p", self.p, sd["p"])
+            self.buffer_index, self.episodes_in_buffer = int(sd["buffer_index"]), int(sd["episodes_in_buffer"])
+        else:
+            self.p.zero_()
+            self.buffer_index, self.episodes_in_buffer = 0, 0
 
     # -- priorities -----------------------------------------------------------------
     def update_priorities(self, idxes, priorities, add=0.0):

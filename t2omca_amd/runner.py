@@ -50,11 +50,14 @@ from ._lib import EP_STATS
 from .distributed import rank as dist_rank, rank_seed, world_size
 from .env import INFO_KEYS
 from .episode_batch import DeviceEpisodeBatch
+from .state import check_fields, copy_checked
 
 # what accumulator slots 2.. sum (include/t2omca.h t2o_episode_stats): the keys of the
 # terminated step's info dict (environment_multi_mec.py:340-363), logged as key + "_mean"
 STAT_KEYS = ("reward",) + INFO_KEYS[:4] + ("episode_limit",) + INFO_KEYS[4:]
 assert len(STAT_KEYS) == EP_STATS - 2
+# the columns of evaluate(per_episode=True)'s rows
+EPISODE_INFO_KEYS = ("return",) + STAT_KEYS
 
 
 class LinearSchedule:
@@ -245,13 +248,55 @@ class RolloutRunner:
         """As train_stats, for the test runs."""
         return self._stats_dict(True)
 
-    def evaluate(self, n_runs=None, new_buffers=True):
+    def evaluate(self, n_runs=None, new_buffers=True, per_episode=False):
         """max(1, test_nepisode // n) greedy runs (per_run.py:240,255-256), after which
-        the test statistics are logged; returns the last run's batch."""
-        batch = None
+        the test statistics are logged; returns the last run's batch.
+
+        per_episode=True: returns (batch, rows) with ``rows`` a CPU fp64 tensor
+        [episodes, len(EPISODE_INFO_KEYS)], one row per evaluated episode in run
+        order: its return and the STAT_KEYS values of its terminal step (NaN for an
+        env that did not terminate) — what evaluate_sequential collects as
+        episode_info (per_run.py:80-94).  One host copy per run."""
+        batch, rows = None, []
         for _ in range(max(1, self.test_nepisode // self.n) if n_runs is None else int(n_runs)):
             batch = self.run(test_mode=True, new_buffers=new_buffers)
-        return batch
+            if per_episode:
+                rows.append(self._episode_rows())
+        return (batch, torch.cat(rows)) if per_episode else batch
+
+    def _episode_rows(self):
+        env = self.env
+        done = env.terminated.double().unsqueeze(1)
+        row = torch.cat([self.last_returns.unsqueeze(1), env.reward.unsqueeze(1), env.info[:, :4], done,
+                         env.info[:, 4:]], dim=1).cpu()
+        row[row[:, 6] == 0, 1:] = float("nan")
+        return row
+
+    # -- saved state (driver.save_run_state) ---------------------------------------------
+    def _built_with(self):
+        s = self.schedule
+        return {"epsilon_schedule": [s.start, s.finish, s.time_length], "precision": self.precision,
+                "compact_obs": self.compact_obs}
+
+    def state_dict(self):
+        """t_env, the episode count (the ε-greedy draw counter), the seed in use, the
+        log schedule's counter and the statistics accumulators.  The env is saved by
+        its own state_dict, not nested here."""
+        return {"format": 1, **self._built_with(), "t_env": int(self.t_env), "episode": int(self.episode),
+                "seed": self.seed, "log_train_stats_t": int(self.log_train_stats_t),
+                "acc": None if self._acc is None else self._acc.detach().cpu(), "n_acc": list(self._n_acc)}
+
+    def load_state_dict(self, sd):
+        check_fields("RolloutRunner", sd, {"format": 1, **self._built_with()})
+        if (sd["acc"] is None) != (self._acc is None):
+            raise ValueError(f"RolloutRunner state: acc (the statistics accumulators) is "
+                             f"{'absent' if sd['acc'] is None else 'present'} in the saved state, "
+                             f"{'absent' if self._acc is None else 'present'} here")
+        if self._acc is not None:
+            copy_checked("RolloutRunner", "acc", self._acc, sd["acc"])
+        self.t_env, self.episode, self.seed = int(sd["t_env"]), int(sd["episode"]), int(sd["seed"])
+        self.log_train_stats_t = int(sd["log_train_stats_t"])
+        self._n_acc = [int(v) for v in sd["n_acc"]]
 
     def _dest(self, tm, t):
         if self.compact_obs:

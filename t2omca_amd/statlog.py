@@ -6,6 +6,10 @@ the driver call (parallel_runner.py:218,224-230, per_run.py:284-285):
 
 ``stats[key]`` is the list of ``(t, value)`` pairs logged under ``key``, as
 PyMARL keeps it.  No tensorboard, no sacred.
+
+``state_dict()`` / ``load_state_dict(sd)`` save and restore ``stats`` (as
+``{key: [[t, value], ...]}``: plain lists, so ``torch.load(weights_only=True)``
+keeps it), for driver.save_run_state.
 """
 from collections import defaultdict
 
@@ -18,6 +22,14 @@ class StatsLogger:
 
     def log_stat(self, key, value, t):
         self.stats[key].append((t, float(value)))
+
+    def state_dict(self):
+        return {"format": 1, "stats": {k: [[t, v] for t, v in rows] for k, rows in self.stats.items()}}
+
+    def load_state_dict(self, sd):
+        if sd.get("format") != 1:
+            raise ValueError(f"StatsLogger state: format {sd.get('format')!r}, expected 1")
+        self.stats = defaultdict(list, {k: [(t, float(v)) for t, v in rows] for k, rows in sd["stats"].items()})
 
     def recent(self):
         """{key: latest value}."""
