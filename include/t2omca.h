@@ -20,6 +20,8 @@
  *   t2o_td_stats           the masked sums the learner's log values come from
  *   t2o_episode_stats      the runner's per-run statistics (parallel_runner.py:202-210)
  *   t2o_adam_step          optimiser step with global-norm clipping
+ *   t2o_td_qlambda         t2o_td_loss with Peng's Q(λ) targets (q_lambda: True)
+ *   t2o_rmsprop_step       the RMSprop optimiser step (optimizer != 'adam')
  *   t2o_env_step / reset   MultiAgvOffloadingEnv.step/reset/get_obs/get_state
  *                          (environment_multi_mec.py:184-366, normalization.py)
  *
@@ -166,6 +168,7 @@ int t2o_unpack_grads(const t2o_layout* L, const float* params, const float* gpac
 #define T2O_ARGS_TAPE 4
 #define T2O_ARGS_TD 5
 #define T2O_ARGS_TD_STATS 6
+#define T2O_ARGS_TD_QLAMBDA 7
 int t2o_args_sizeof(int which); /* sizeof the T2O_ARGS_* struct, -1 for an unknown one */
 
 /* Agent unroll forward (TransformerAgent.forward over t, transf_agent.py:54-76) for
@@ -368,7 +371,8 @@ int t2o_bwd_tape_contract(const t2o_tape_args* first, const t2o_tape_args* secon
 
 /* TD loss algorithms */
 #define T2O_TD_AUTO 0        /* the library's default (currently T2O_TD_WAVE_SCAN, the faster) */
-#define T2O_TD_SEQUENTIAL 1  /* one thread per episode, the reference's backward order (T <= ~4900) */
+#define T2O_TD_SEQUENTIAL 1  /* one thread per episode, the reference's backward order (t2o_td_loss:
+                                T <= 4915; t2o_td_qlambda, one more staged row: T <= 4095) */
 #define T2O_TD_WAVE_SCAN 2   /* one wave per episode: suffix scan of the linear TD(λ) recursion
                                 (reassociated: fp32 rounding differs by ~1e-7 relative; any T) */
 
@@ -398,6 +402,44 @@ typedef struct {
   int32_t B, T;
 } t2o_td_args;
 int t2o_td_loss(const t2o_td_args* a, void* stream);
+
+/* Peng's Q(λ) targets (PyMARL2 build_q_lambda_targets, NQLearner q_lambda: True)
+ * in place of the TD(λ) ones; everything else — mask m, loss, gq, prio, loss[2],
+ * mask_sum / mask_sum_acc, mask dtypes, priority 0 of an all-masked episode,
+ * algo — as t2o_td_loss.  With Q' = qtot_tgt, Qk = qtot_taken:
+ *   ret_T = Q'_T (1 - Σ_t term_t)
+ *   ret_t = λγ ret_{t+1} + m_t (r_t + (Q'_t - Qk_t) + (1-λ)γ Q'_{t+1} (1 - term_t)),  t = T-1 .. 0
+ *   targets = ret_{0..T-1}
+ * The correction (Q'_t - Qk_t) is formed first and then added to r_t: with
+ * qtot_taken equal to qtot_tgt it is an exact zero and the outputs are
+ * t2o_td_loss's bit for bit.  T2O_TD_SEQUENTIAL stages one more row per episode
+ * in LDS than t2o_td_loss does: T2O_EUNSUPPORTED beyond T = 4095 (there 4915);
+ * the wave scan takes any T.  (Added within ABI 6: nothing existing moved.) */
+typedef struct {
+  const float* qtot;          /* the fields of t2o_td_args, in its order ... */
+  const float* qtot_tgt;
+  const float* reward;
+  int64_t rw_sb, rw_st;
+  const void* term;
+  int64_t tm_sb, tm_st;
+  const void* filled;
+  int64_t fl_sb, fl_st;
+  const float* per_weight;
+  float* gq;
+  float* targets;
+  float* prio;
+  float* loss;
+  float* mask_sum_acc;
+  float gamma, td_lambda;
+  float mask_sum;
+  int32_t term_dtype, filled_dtype;
+  int32_t algo;
+  int32_t B, T;
+  const float* qtot_taken;    /* ... then: the target mixer on the target Q at the taken actions;
+                                 row b starts at b * qk_sb, steps 0..T-1 are read */
+  int64_t qk_sb;              /* >= T (the producer may unroll T or T+1 steps) */
+} t2o_td_qlambda_args;
+int t2o_td_qlambda(const t2o_td_qlambda_args* a, void* stream);
 
 /* ---- logged statistics (t2o_stats.hip).  Both entry points run one workgroup,
  * accumulate in fp64 without atomics and combine their partial sums in a fixed
@@ -446,6 +488,15 @@ int t2o_adam_step(float* params, const float* grads, float* exp_avg, float* exp_
                   float weight_decay, float max_grad_norm, int64_t step, const float* grad_div,
                   float* grad_norm_out, void* stream);
 int t2o_adam_workspace_floats(void);
+
+/* clip_grad_norm_(max_grad_norm) + torch.optim.RMSprop (momentum 0, not centered)
+ * over n floats:  g += weight_decay p;  square_avg = α square_avg + (1-α) g²;
+ * p -= lr g / (sqrt(square_avg) + eps).  workspace (t2o_adam_workspace_floats()
+ * floats), grad_div and grad_norm_out as t2o_adam_step.  T2O_EINVAL before any
+ * launch for a null required pointer or n < 1.  (Added within ABI 6.) */
+int t2o_rmsprop_step(float* params, const float* grads, float* square_avg, float* workspace, int64_t n,
+                     double lr, double alpha, float eps, float weight_decay, float max_grad_norm,
+                     const float* grad_div, float* grad_norm_out, void* stream);
 
 /* Diagnostic: runs the cross-lane primitives the kernels rely on (4-lane
  * all-reduces via ds_bpermute and via gfx950 permlane swaps, 16-lane DPP row

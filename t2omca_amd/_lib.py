@@ -79,7 +79,10 @@ TDArgs = _args_class("TDArgs", 5, """qtot:P, qtot_tgt:P, reward:P, rw_sb:J, rw_s
     td_lambda:F, mask_sum:F, term_dtype:I, filled_dtype:I, algo:I, B:I, T:I""")
 TDStatsArgs = _args_class("TDStatsArgs", 6, """qtot:P, targets:P, term:P, tm_sb:J, tm_st:J, filled:P, fl_sb:J,
     fl_st:J, term_dtype:I, filled_dtype:I, B:I, T:I, out:P""")
-ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs)
+TDQLambdaArgs = _args_class("TDQLambdaArgs", 7, """qtot:P, qtot_tgt:P, reward:P, rw_sb:J, rw_st:J, term:P, tm_sb:J,
+    tm_st:J, filled:P, fl_sb:J, fl_st:J, per_weight:P, gq:P, targets:P, prio:P, loss:P, mask_sum_acc:P, gamma:F,
+    td_lambda:F, mask_sum:F, term_dtype:I, filled_dtype:I, algo:I, B:I, T:I, qtot_taken:P, qk_sb:J""")
+ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs, TDQLambdaArgs)
 EP_STATS = 10  # include/t2omca.h T2O_EP_STATS
 
 
@@ -123,6 +126,9 @@ EXPORTS = {
     "t2o_adam_step": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_double] * 3 +
                       [ctypes.c_float] * 3 + [ctypes.c_int64] + [ctypes.c_void_p] * 3),
     "t2o_adam_workspace_floats": (ctypes.c_int, []),
+    "t2o_td_qlambda": (ctypes.c_int, [ctypes.POINTER(TDQLambdaArgs), ctypes.c_void_p]),
+    "t2o_rmsprop_step": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_double] * 2 +
+                         [ctypes.c_float] * 3 + [ctypes.c_void_p] * 3),
     "t2o_probe_lane_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_scatter_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_xdl_hazards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -153,11 +159,12 @@ EXPORTS = {
 _DIAGNOSTIC = {"t2o_bf_swz", "t2o_probe_lane_ops", "t2o_probe_scatter_ops", "t2o_probe_posf", "t2o_probe_xdl_hazards",
                "t2o_layout_instance",
                "t2o_abi_version"}
-# the logged statistics (same ABI version: nothing existing moved), which a build
-# from before them lacks; calling one on such a library raises AttributeError
-_OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats"}
+# the logged statistics, the Q(λ) targets and the RMSprop step (same ABI version:
+# nothing existing moved), which a build from before them lacks; calling one on such
+# a library raises AttributeError
+_OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats", "t2o_td_qlambda", "t2o_rmsprop_step"}
 # argument structs of optional exports: no size to check where the export is absent
-_STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats"}
+_STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats", TDQLambdaArgs: "t2o_td_qlambda"}
 
 _lib = None
 

@@ -11,7 +11,14 @@
 //   prio_b   = Σ_t |td| m / √(Σ_t m)
 // and torch.nn.utils.clip_grad_norm_ + torch.optim.Adam (non-amsgrad, L2
 // weight decay) on the flat parameter buffer.
+// The learner's two other switches (q_lambda, optimizer != 'adam'):
+//   targets  = build_q_lambda_targets(r, term, mask, Qtot_tgt[0..T], Qtot_taken[0..T-1], γ, λ)
+// (Peng's Q(λ): r_t gains the off-policy correction Qtot_tgt_t - Qtot_taken_t), the same
+// kernels instantiated with QL = true, and clip_grad_norm_ + torch.optim.RMSprop
+// (momentum 0, not centered).
 #include <math.h>
+
+#include <type_traits>
 
 #include "t2o_common.hpp"
 
@@ -35,6 +42,14 @@ struct TDArgs {
   int B, T;
   int tm_dt, fl_dt;       // T2O_DT_* (t2omca.h): the EpisodeBatch's own dtypes, read in place
 };
+
+// Q(λ): the TD arguments and the target mixer's output on the target Q of the taken actions
+struct TDQArgs : TDArgs {
+  const float* qk;        // [B][>=T], row stride qk_sb
+  int64_t qk_sb;
+};
+template <bool QL>
+using TDArgsOf = std::conditional_t<QL, TDQArgs, TDArgs>;
 
 // one 0/1 mask element of the given storage type as float
 __device__ float mask_at(const void* p, int64_t i, int dt) {
@@ -64,7 +79,10 @@ __device__ float block_sum(float v, float* red) {
 // into loss[] (zeroed by the host entry); with mask_sum <= 0 a second pass
 // divides gq and the loss by the local Σ mask.
 //   mask[b][t] = filled[t] * (t == 0 ? 1 : 1 - term[t-1])   (PyMARL2 nq_learner)
-__global__ __launch_bounds__(256) void td_loss_kernel(TDArgs a, int EP) {
+// QL: one more staged row per episode (qtot_taken); r_t + (Q'_t - Qk_t) takes r_t's
+// place in the recursion, the correction formed first (an exact 0 where Qk = Q').
+template <bool QL>
+__global__ __launch_bounds__(256) void td_loss_kernel(TDArgsOf<QL> a, int EP) {
   extern __shared__ float sm[];
   T2O_LDS_POISON(sm);
   __shared__ float red[8];
@@ -76,8 +94,10 @@ __global__ __launch_bounds__(256) void td_loss_kernel(TDArgs a, int EP) {
   float* FL = TM + EP * T;       // filled, then targets
   float* Q = FL + EP * T;        // qtot
   float* QT = Q + EP * T;        // qtot_tgt [EP][T+1]
+  [[maybe_unused]] float* QK = QT + EP * (T + 1);  // QL: qtot_taken [EP][T]
   for (int i = threadIdx.x; i < nb * T; i += blockDim.x) {
     const int b = b0 + i / T, t = i % T;
+    if constexpr (QL) QK[i] = a.qk[b * a.qk_sb + t];
     R[i] = a.reward[b * a.rw_sb + t * a.rw_st];
     TM[i] = a.term ? mask_at(a.term, b * a.tm_sb + t * a.tm_st, a.tm_dt) : 0.f;
     FL[i] = a.filled ? mask_at(a.filled, b * a.fl_sb + t * a.fl_st, a.fl_dt) : 1.f;
@@ -102,7 +122,9 @@ __global__ __launch_bounds__(256) void td_loss_kernel(TDArgs a, int EP) {
     float absum = 0.f, mb = 0.f, lb = 0.f;
     for (int t = T - 1; t >= 0; --t) {
       const float m = fl[t] * (t > 0 ? 1.f - tm[t - 1] : 1.f);
-      ret = a.lambda_ * a.gamma * ret + m * (r[t] + (1.f - a.lambda_) * a.gamma * qt[t + 1] * (1.f - tm[t]));
+      float rt = r[t];
+      if constexpr (QL) rt += qt[t] - QK[e * T + t];
+      ret = a.lambda_ * a.gamma * ret + m * (rt + (1.f - a.lambda_) * a.gamma * qt[t + 1] * (1.f - tm[t]));
       const float td = q[t] - ret;
       // in-place: row t of R / FL is not read again
       R[e * T + t] = w * m * td / denom;
@@ -138,9 +160,11 @@ __global__ __launch_bounds__(256) void td_loss_kernel(TDArgs a, int EP) {
 // re-runs the recursion from it.  Reassociated (fp32 rounding differs from the
 // sequential order by ~1e-7 relative), deterministic, and the T-step serial
 // chain becomes C + 6 steps.
+// QL: B_t (t < T) gains m_t (Q'_t - Qk_t); the multiplier stays λγ.
 constexpr int TDW_WAVES = 4;
 
-__global__ __launch_bounds__(64 * TDW_WAVES) void td_loss_wave_kernel(TDArgs a) {
+template <bool QL>
+__global__ __launch_bounds__(64 * TDW_WAVES) void td_loss_wave_kernel(TDArgsOf<QL> a) {
   __shared__ float red[2][TDW_WAVES];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int b = blockIdx.x * TDW_WAVES + w;
@@ -160,7 +184,9 @@ __global__ __launch_bounds__(64 * TDW_WAVES) void td_loss_wave_kernel(TDArgs a) 
     auto mask = [&](int t) { return fl(t) * (t > 0 ? 1.f - tm(t - 1) : 1.f); };
     auto Bt = [&](int t) {
       if (t == T) return qt[T] * (1.f - ts);
-      return mask(t) * (a.reward[(int64_t)b * a.rw_sb + (int64_t)t * a.rw_st] + G1 * qt[t + 1] * (1.f - tm(t)));
+      float rt = a.reward[(int64_t)b * a.rw_sb + (int64_t)t * a.rw_st];
+      if constexpr (QL) rt += qt[t] - a.qk[(int64_t)b * a.qk_sb + t];
+      return mask(t) * (rt + G1 * qt[t + 1] * (1.f - tm(t)));
     };
     float g = 0.f, p = 1.f;
     for (int t = t1 - 1; t >= t0; --t) {
@@ -276,50 +302,99 @@ __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
   }
 }
 
+// ---- RMSprop (torch.optim.RMSprop, momentum 0, not centered) -------------------
+struct RmspropArgs {
+  float* p;
+  const float* g;
+  float* sq;
+  const float* part;  // as AdamArgs
+  const float* gdiv;
+  float* norm_out;
+  int64_t n;
+  float lr, alpha, oma, eps, weight_decay, max_norm;  // oma = 1-α (rounded from double)
+};
+
+__global__ __launch_bounds__(256) void rmsprop_kernel(RmspropArgs a) {
+  // the clip coefficient exactly as adam_kernel forms it
+  const float inv = a.gdiv ? 1.0f / a.gdiv[0] : 1.0f;
+  float coef = inv;
+  if (a.part) {
+    float s = 0.f;
+    for (int i = 0; i < NORM_BLOCKS; ++i) s += a.part[i];
+    const float norm = sqrtf(s) * inv;
+    coef = inv * fminf(a.max_norm / (norm + 1e-6f), 1.0f);
+    if (a.norm_out && blockIdx.x == 0 && threadIdx.x == 0) a.norm_out[0] = norm;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * blockDim.x) {
+    float g = a.g[i] * coef;
+    const float p = a.p[i];
+    if (a.weight_decay != 0.f) g += a.weight_decay * p;
+    const float sq = a.sq[i] * a.alpha + g * g * a.oma;  // square_avg.mul_(α).addcmul_(g, g, 1-α)
+    a.sq[i] = sq;
+    a.p[i] = p - a.lr * (g / (sqrtf(sq) + a.eps));       // p.addcdiv_(g, sqrt(sq) + eps, -lr)
+  }
+}
+
 }  // namespace
 
-static int td_impl(const float* qtot, const float* qtot_tgt, const float* reward, int64_t rw_sb,
-                               int64_t rw_st, const void* term, int term_dtype, int64_t tm_sb, int64_t tm_st,
-                               const void* filled, int filled_dtype, int64_t fl_sb, int64_t fl_st,
-                               const float* per_weight, float gamma, float td_lambda, float mask_sum, float* gq,
-                               float* targets, float* prio, float* loss, float* mask_sum_acc, int algo, int B,
-                               int T, void* stream) {
-  if (!qtot || !qtot_tgt || !reward || !gq || !prio || !loss || B < 1 || T < 1) return T2O_EINVAL;
+// QL = false: t2o_td_loss, exactly as before Q(λ) existed (the same kernels' TD(λ)
+// instantiations, argument struct and LDS sizes); QL = true: t2o_td_qlambda.
+template <bool QL>
+static int td_impl(const TDArgsOf<QL>& a, int algo, void* stream) {
+  const int B = a.B, T = a.T;
+  if (!a.qtot || !a.qtot_tgt || !a.reward || !a.gq || !a.prio || !a.loss || B < 1 || T < 1) return T2O_EINVAL;
+  if constexpr (QL)
+    if (!a.qk || a.qk_sb < T) return T2O_EINVAL;
   auto dt_ok = [](int dt) { return dt == T2O_DT_F32 || dt == T2O_DT_U8 || dt == T2O_DT_I32 || dt == T2O_DT_I64; };
-  if (!dt_ok(term_dtype) || !dt_ok(filled_dtype)) return T2O_EINVAL;
+  if (!dt_ok(a.tm_dt) || !dt_ok(a.fl_dt)) return T2O_EINVAL;
   if (algo < T2O_TD_AUTO || algo > T2O_TD_WAVE_SCAN) return T2O_EINVAL;
-  TDArgs a{qtot, qtot_tgt, reward, term, filled, per_weight, rw_sb, rw_st, tm_sb, tm_st, fl_sb, fl_st,
-           gamma, td_lambda, mask_sum, gq, targets, prio, loss, mask_sum_acc, B, T, term_dtype, filled_dtype};
   hipStream_t s = (hipStream_t)stream;
   // AUTO = the wave scan: 8-10 us faster per configs[2] update than the sequential
   // kernel (interleaved, profiles/r4_a/), parity equal (tests/test_gpu_td_loss.py)
   const bool wave = algo != T2O_TD_SEQUENTIAL;
-  if (hipMemsetAsync(loss, 0, 2 * sizeof(float), s) != hipSuccess) return (int)hipGetLastError();
+  // the sequential kernel's rows per episode in LDS: reward, term, filled, qtot,
+  // qtot_tgt [T+1] (+ qtot_taken)
+  const size_t per_ep = sizeof(float) * ((QL ? 6 : 5) * (size_t)T + 1);
+  // episodes per workgroup: few enough that the grid covers the CUs (the
+  // staging loads, not the per-episode scan, dominate a fat workgroup)
+  int ep = (int)((96 * 1024) / per_ep);
+  if (ep > 64) ep = 64;
+  const int ep_fill = (B + 255) / 256;
+  if (ep > ep_fill) ep = ep_fill;
+  // T beyond the LDS staging (TD(λ): > 4915 steps, Q(λ): > 4095): use the wave scan
+  if (!wave && ep < 1) return T2O_EUNSUPPORTED;
+  if (hipMemsetAsync(a.loss, 0, 2 * sizeof(float), s) != hipSuccess) return (int)hipGetLastError();
   if (wave) {
-    hipLaunchKernelGGL(td_loss_wave_kernel, dim3((B + TDW_WAVES - 1) / TDW_WAVES), dim3(64 * TDW_WAVES), 0, s, a);
+    hipLaunchKernelGGL(td_loss_wave_kernel<QL>, dim3((B + TDW_WAVES - 1) / TDW_WAVES), dim3(64 * TDW_WAVES), 0, s, a);
   } else {
-    const size_t per_ep = sizeof(float) * (5 * (size_t)T + 1);
-    // episodes per workgroup: few enough that the grid covers the CUs (the
-    // staging loads, not the per-episode scan, dominate a fat workgroup)
-    int ep = (int)((96 * 1024) / per_ep);
-    if (ep > 64) ep = 64;
-    const int ep_fill = (B + 255) / 256;
-    if (ep > ep_fill) ep = ep_fill;
-    if (ep < 1) return T2O_EUNSUPPORTED;  // T beyond the LDS staging (> ~4900 steps): use the wave scan
-    (void)hipFuncSetAttribute((const void*)td_loss_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)td_loss_kernel<QL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(ep * per_ep));
-    hipLaunchKernelGGL(td_loss_kernel, dim3((B + ep - 1) / ep), dim3(256), ep * per_ep, s, a, ep);
+    hipLaunchKernelGGL(td_loss_kernel<QL>, dim3((B + ep - 1) / ep), dim3(256), ep * per_ep, s, a, ep);
   }
-  if (mask_sum <= 0.f)
-    hipLaunchKernelGGL(td_normalise_kernel, dim3(1), dim3(256), 0, s, gq, (int64_t)B * T, loss);
+  if (a.mask_sum <= 0.f)
+    hipLaunchKernelGGL(td_normalise_kernel, dim3(1), dim3(256), 0, s, a.gq, (int64_t)B * T, a.loss);
   return (int)hipGetLastError();
+}
+
+template <class A>
+static TDArgs td_args_of(const A* a) {
+  return TDArgs{a->qtot, a->qtot_tgt, a->reward, a->term, a->filled, a->per_weight, a->rw_sb, a->rw_st,
+                a->tm_sb, a->tm_st, a->fl_sb, a->fl_st, a->gamma, a->td_lambda, a->mask_sum, a->gq,
+                a->targets, a->prio, a->loss, a->mask_sum_acc, a->B, a->T, a->term_dtype, a->filled_dtype};
 }
 
 extern "C" int t2o_td_loss(const t2o_td_args* a, void* stream) {
   if (!a) return T2O_EINVAL;
-  return td_impl(a->qtot, a->qtot_tgt, a->reward, a->rw_sb, a->rw_st, a->term, a->term_dtype, a->tm_sb, a->tm_st,
-                 a->filled, a->filled_dtype, a->fl_sb, a->fl_st, a->per_weight, a->gamma, a->td_lambda, a->mask_sum,
-                 a->gq, a->targets, a->prio, a->loss, a->mask_sum_acc, a->algo, a->B, a->T, stream);
+  return td_impl<false>(td_args_of(a), a->algo, stream);
+}
+
+extern "C" int t2o_td_qlambda(const t2o_td_qlambda_args* a, void* stream) {
+  if (!a) return T2O_EINVAL;
+  TDQArgs q{};
+  static_cast<TDArgs&>(q) = td_args_of(a);
+  q.qk = a->qtot_taken;
+  q.qk_sb = a->qk_sb;
+  return td_impl<true>(q, a->algo, stream);
 }
 
 extern "C" int t2o_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
@@ -358,3 +433,32 @@ extern "C" int t2o_adam_step(float* params, const float* grads, float* exp_avg, 
 }
 
 extern "C" int t2o_adam_workspace_floats(void) { return NORM_BLOCKS; }
+
+extern "C" int t2o_rmsprop_step(float* params, const float* grads, float* square_avg, float* workspace, int64_t n,
+                                double lr, double alpha, float eps, float weight_decay, float max_grad_norm,
+                                const float* grad_div, float* grad_norm_out, void* stream) {
+  if (!params || !grads || !square_avg || n < 1) return T2O_EINVAL;
+  if (max_grad_norm > 0.f && !workspace) return T2O_EINVAL;
+  RmspropArgs a{};
+  a.p = params;
+  a.g = grads;
+  a.sq = square_avg;
+  a.n = n;
+  a.lr = (float)lr;
+  a.alpha = (float)alpha;
+  a.oma = (float)(1.0 - alpha);
+  a.eps = eps;
+  a.weight_decay = weight_decay;
+  a.max_norm = max_grad_norm;
+  a.norm_out = grad_norm_out;
+  a.gdiv = grad_div;
+  hipStream_t s = (hipStream_t)stream;
+  if (max_grad_norm > 0.f) {
+    hipLaunchKernelGGL(sqnorm_partials, dim3(NORM_BLOCKS), dim3(256), 0, s, grads, n, workspace);
+    a.part = workspace;
+  }
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(rmsprop_kernel, dim3(blocks), dim3(256), 0, s, a);
+  return (int)hipGetLastError();
+}

@@ -345,6 +345,7 @@ extern "C" int t2o_args_sizeof(int which) {
     case T2O_ARGS_TAPE: return (int)sizeof(t2o_tape_args);
     case T2O_ARGS_TD: return (int)sizeof(t2o_td_args);
     case T2O_ARGS_TD_STATS: return (int)sizeof(t2o_td_stats_args);
+    case T2O_ARGS_TD_QLAMBDA: return (int)sizeof(t2o_td_qlambda_args);
     default: return -1;
   }
 }

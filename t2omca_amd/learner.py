@@ -15,7 +15,10 @@ priorities are copied out):
   agent unroll fwd, online + target, t = 0..T      t2o_agent_unroll_fwd (1 launch)
   mixer unroll fwd, online (chosen Q, t < T) +
         target (double-Q, t <= T)                  t2o_mixer_unroll_fwd (1 launch)
+  [q_lambda: mixer unroll fwd, the target mixer on
+   the target Q at the taken actions, t < T        t2o_mixer_unroll_fwd (one network)]
   TD(λ) targets, loss, dL/dQtot, priorities        t2o_td_loss
+  [q_lambda: Peng's Q(λ) targets instead           t2o_td_qlambda]
   mixer BPTT -> dL/dq_chosen, dL/dhidden           t2o_mixer_unroll_bwd
   mixer tape contraction + slab sum + unfold       side stream, issued here; it
                                                    runs as the agent BPTT's waves drain
@@ -26,6 +29,7 @@ priorities are copied out):
    whose waves hold every SIMD]
   (contract="pair": both tapes in one launch after the agent BPTT, one all-reduce)
   clip_grad_norm_ + Adam                           t2o_adam_step
+  [optimizer="rmsprop": clip_grad_norm_ + RMSprop  t2o_rmsprop_step]
 """
 import dataclasses
 import os
@@ -37,6 +41,21 @@ import torch.distributed as dist
 from . import ops
 from .distributed import allreduce_async, broadcast_state, wait_all
 from .state import check_fields, copy_checked
+
+
+OPTIMIZERS = {"adam": "Adam", "rmsprop": "RMSprop"}  # TDLearner(optimizer=...): the torch.optim class of opt.th
+
+
+def _optimiser_of(opt_state):
+    """Which of OPTIMIZERS wrote this torch optimiser state_dict (None: neither): by
+    its per-parameter state, or, saved before the first step, by its param_groups."""
+    seen = [st for st in opt_state.get("state", {}).values() if st] or list(opt_state.get("param_groups", []))
+    for d in seen:
+        if "exp_avg" in d or "betas" in d:
+            return "adam"
+        if "square_avg" in d or "alpha" in d:
+            return "rmsprop"
+    return None
 
 
 def _bind_flat(modules, device):
@@ -58,7 +77,7 @@ class TDLearner:
                  target_update_interval=200, optim_betas=(0.9, 0.999), optim_eps=1e-8, weight_decay=0.0,
                  detach_mixer_hidden=False, process_group=None, priorities_to_cpu=True, precision="fp32",
                  overlap=True, td_algo="auto", contract="side", pipeline="auto", pipeline_ranges=6,
-                 logger=None, learner_log_interval=10000):
+                 logger=None, learner_log_interval=10000, q_lambda=False, optimizer="adam", optim_alpha=0.99):
         # options first (a bad value fails here, not inside the first train())
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
@@ -71,6 +90,12 @@ class TDLearner:
         if pipeline is True and (contract == "pair" or not overlap):
             raise ValueError("pipeline=True runs the mixer's contraction on the side stream: it needs "
                              "contract='side' and overlap=True")
+        if q_lambda not in (True, False):
+            raise ValueError(f"q_lambda must be True or False, got {q_lambda!r}")
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {list(OPTIMIZERS)}, got {optimizer!r}")
+        if not 0.0 <= float(optim_alpha) < 1.0:
+            raise ValueError(f"optim_alpha must lie in [0, 1), got {optim_alpha!r}")
         dev = next(agent.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("TDLearner needs the modules on a HIP device (no CPU fallback)")
@@ -88,6 +113,7 @@ class TDLearner:
         self.device = dev
         self.params = _bind_flat([agent, mixer], dev)
         self.grad = torch.zeros(self.na + self.nm + 1, device=dev)  # last slot: Σ mask
+        # (optimizer="rmsprop": exp_avg_sq is RMSprop's square_avg and exp_avg stays zero)
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
         self.target_params = self.params.clone()
@@ -99,6 +125,9 @@ class TDLearner:
         self.adam_ws = torch.empty(int(ops.lib().t2o_adam_workspace_floats()), device=dev)
         self.grad_norm = torch.zeros(1, device=dev)
         self.lr, self.betas, self.eps, self.wd = lr, optim_betas, optim_eps, weight_decay
+        # PyMARL2 NQLearner's two other switches: Peng's Q(λ) targets (args.q_lambda) and
+        # RMSprop(lr, alpha=optim_alpha, eps=optim_eps) (args.optimizer != 'adam')
+        self.q_lambda, self.optimizer, self.alpha = bool(q_lambda), optimizer, float(optim_alpha)
         self.gamma, self.td_lambda, self.clip = gamma, td_lambda, grad_norm_clip
         self.target_update_interval = target_update_interval
         self.detach_mixer_hidden = detach_mixer_hidden
@@ -193,24 +222,33 @@ class TDLearner:
         return self
 
     def _optimiser_view(self):
-        """A torch.optim.Adam over the modules' parameters (mac then mixer, the
-        order of a PyMARL2 NQLearner's optimiser) carrying this learner's moments,
-        so opt.th is a standard Adam state_dict."""
+        """A torch.optim.Adam (or RMSprop) over the modules' parameters (mac then
+        mixer, the order of a PyMARL2 NQLearner's optimiser) carrying this learner's
+        moments, so opt.th is that optimiser's standard state_dict."""
         params = list(self.agent.parameters()) + list(self.mixer.parameters())
-        opt = torch.optim.Adam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
+        if self.optimizer == "rmsprop":
+            opt = torch.optim.RMSprop(params, lr=self.lr, alpha=self.alpha, eps=self.eps, weight_decay=self.wd)
+        else:
+            opt = torch.optim.Adam(params, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
         off = 0
         for p in params:
             k = p.numel()
             if self.step_count:
-                opt.state[p] = {"step": torch.tensor(float(self.step_count)),
-                                "exp_avg": self.exp_avg[off:off + k].view_as(p),
-                                "exp_avg_sq": self.exp_avg_sq[off:off + k].view_as(p)}
+                opt.state[p] = {"step": torch.tensor(float(self.step_count))}
+                for name, buf in self._moments():
+                    opt.state[p][name] = buf[off:off + k].view_as(p)
             off += k
         return opt
 
+    def _moments(self):
+        """(name in the torch optimiser's per-parameter state, flat buffer) pairs."""
+        if self.optimizer == "rmsprop":
+            return (("square_avg", self.exp_avg_sq),)
+        return (("exp_avg", self.exp_avg), ("exp_avg_sq", self.exp_avg_sq))
+
     def save_models(self, path):
         """PyMARL layout: {path}/agent.th, mixer.th (reference state_dict keys) and
-        opt.th (torch Adam state_dict)."""
+        opt.th (torch Adam / RMSprop state_dict)."""
         torch.save(self.agent.state_dict(), os.path.join(path, "agent.th"))
         torch.save(self.mixer.state_dict(), os.path.join(path, "mixer.th"))
         torch.save(self._optimiser_view().state_dict(), os.path.join(path, "opt.th"))
@@ -218,29 +256,36 @@ class TDLearner:
     def load_models(self, path):
         """Inverse of save_models; also takes checkpoints written by the reference
         framework.  As PyMARL2's NQLearner does, the target agent is reloaded from
-        agent.th and the target mixer is left as it is; opt.th is optional."""
+        agent.th and the target mixer is left as it is; opt.th is optional, and one
+        written by the other optimiser is a ValueError naming both."""
         def load(name):
             return torch.load(os.path.join(path, name), map_location=self.device, weights_only=True)
+        saved = load("opt.th") if os.path.exists(os.path.join(path, "opt.th")) else None
+        held = _optimiser_of(saved) if saved is not None else None
+        if held is not None and held != self.optimizer:  # (before anything is overwritten)
+            raise ValueError(f"opt.th holds the state of a {OPTIMIZERS[held]} optimiser, this learner runs "
+                             f"{OPTIMIZERS[self.optimizer]} (optimizer={self.optimizer!r})")
         with torch.no_grad():
             self.agent.load_state_dict(load("agent.th"))  # copies into the flat-buffer views
             self.mixer.load_state_dict(load("mixer.th"))
             self.target_params[:self.na].copy_(self.params[:self.na])
-        if not os.path.exists(os.path.join(path, "opt.th")):
+        if saved is None:
             self._sync_replicas()
             return
         opt = self._optimiser_view()
-        opt.load_state_dict(load("opt.th"))
+        opt.load_state_dict(saved)
         off, steps = 0, set()
         for p in list(self.agent.parameters()) + list(self.mixer.parameters()):
             k = p.numel()
             st = opt.state.get(p)
             if st:
-                self.exp_avg[off:off + k].copy_(st["exp_avg"].reshape(-1))
-                self.exp_avg_sq[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
+                for name, buf in self._moments():
+                    buf[off:off + k].copy_(st[name].reshape(-1))
                 steps.add(int(float(st["step"])))
             off += k
         if len(steps) > 1:
-            raise ValueError(f"opt.th: parameters carry different Adam step counts {sorted(steps)}")
+            raise ValueError(f"opt.th: parameters carry different {OPTIMIZERS[self.optimizer]} step counts "
+                             f"{sorted(steps)}")
         self.step_count = steps.pop() if steps else 0
         self._sync_replicas()
 
@@ -256,14 +301,23 @@ class TDLearner:
                 "exp_avg": self.exp_avg.detach().cpu(), "exp_avg_sq": self.exp_avg_sq.detach().cpu(),
                 "step_count": int(self.step_count),
                 "last_target_update_episode": int(self.last_target_update_episode),
-                "log_stats_t": int(self.log_stats_t)}
+                "log_stats_t": int(self.log_stats_t),
+                # (optim_alpha as a 0-d fp64 tensor: every value here is a tensor, an int or a str)
+                "q_lambda": self.q_lambda, "optimizer": self.optimizer,
+                "optim_alpha": torch.tensor(self.alpha, dtype=torch.float64)}
 
     def load_state_dict(self, sd):
         """In place into the flat buffers, which the modules' parameters view; then
         _sync_replicas: the modules' pack caches dropped, the targets re-packed and
         data-parallel ranks aligned (a collective with a process group).  ValueError
-        naming the field when the parameter counts or the precision differ."""
-        check_fields("TDLearner", sd, {"format": 1, "na": self.na, "nm": self.nm, "precision": self.precision})
+        naming the field when the parameter counts, the precision, the targets
+        (q_lambda) or the optimiser differ; a state saved before the last three
+        existed holds their defaults."""
+        sd = {"q_lambda": False, "optimizer": "adam", "optim_alpha": 0.99, **sd}
+        sd["optim_alpha"] = float(sd["optim_alpha"])
+        check_fields("TDLearner", sd, {"format": 1, "na": self.na, "nm": self.nm, "precision": self.precision,
+                                       "q_lambda": self.q_lambda, "optimizer": self.optimizer,
+                                       "optim_alpha": self.alpha})
         with torch.no_grad():
             for name in ("params", "target_params", "exp_avg", "exp_avg_sq"):
                 copy_checked("TDLearner", name, getattr(self, name), sd[name])
@@ -373,6 +427,10 @@ class TDLearner:
                     mixer_go(1, t0, t1)
             with torch.cuda.stream(side):
                 mixer_go(2)
+            if self.q_lambda:
+                # main has run the last agent range and is idle while the side stream
+                # finishes the mixers: the taken mix goes here, beside them
+                o_tk = self._taken_mix(state, h_tg, q_tg, act, B, T)
             main.wait_stream(side)
         else:
             # 1. agents: online + target over t = 0..T
@@ -382,12 +440,24 @@ class TDLearner:
             main.wait_event(mixer_packed)
             o_on, o_tg = ops.mixer_unroll_fwd(self.sm, self.pack_m, state, h_on, q_on=q_on, hid_tg=h_tg, q_tg=q_tg,
                                               **mixer_kw)
+            if self.q_lambda:
+                # the taken mix after them on this stream: at a batch that fills the chip
+                # a second stream buys nothing (measured)
+                o_tk = self._taken_mix(state, h_tg, q_tg, act, B, T)
         # 3. TD(λ) targets / loss (un-normalised: Σ mask is applied in Adam so the
         #    data-parallel sum over ranks divides by the GLOBAL Σ mask)
         #    (Σ mask also lands in grad[-1] straight from the kernel: grad was cleared
         #    on the side stream before the mixer forward, which waited for it)
-        td = ops.td_loss(o_on["y"], o_tg["y"], reward, term, filled, w, gamma=self.gamma,
-                         td_lambda=self.td_lambda, mask_sum=1.0, algo=self.td_algo, mask_sum_acc=self.grad[-1:])
+        td_kw = dict(gamma=self.gamma, td_lambda=self.td_lambda, mask_sum=1.0, algo=self.td_algo,
+                     mask_sum_acc=self.grad[-1:])
+        if self.q_lambda:
+            # Peng's Q(λ): Qtot_tgt_t - Qtot_taken_t corrects every step's reward (the taken
+            # mix ran on this stream, the target mix on it or on the side stream joined above)
+            td = ops.td_qlambda(o_on["y"], o_tg["y"], o_tk["y"], reward, term, filled, w, **td_kw)
+            # (o_tk, and the pipelined path's o_tg: buffers the next update reuses)
+            td["qtot_taken"], td["qtot_tgt"] = o_tk["y"].clone(), o_tg["y"].clone() if piped else o_tg["y"]
+        else:
+            td = ops.td_loss(o_on["y"], o_tg["y"], reward, term, filled, w, **td_kw)
         # 4. mixer BPTT (its weight-grad tape is contracted after the agent BPTT)
         tape_m = self._slab("tape_m", ops.tape_floats(self.sm, ops.mixer_tape_tiles(B, T, A, self.sm)))
         tape_a = self._slab("tape_a", ops.tape_floats(self.sa, ops.agent_tape_tiles(B, T, A)))
@@ -457,6 +527,18 @@ class TDLearner:
             wait_all((work_m, work_a))
         return self._finish(episode_num, td, o_on, t_env, term, filled)
 
+    def _taken_mix(self, state, h_tg, q_tg, act, B, T):
+        """q_lambda: the target mixer once more, on the target Q at the batch's actions
+        (t < T; qmode 1 from q_tg, the target agents' hidden states) — a one-network
+        t2o_mixer_unroll_fwd, whole, on the current stream, which must be ordered after
+        the target agent unroll.  Into buffers the learner keeps (allocated once and
+        reused every update, like the pipelined update's other forward buffers)."""
+        A, E = self.sm.agents, self.sm.E
+        o_tk = {"y": self._buf("ytk", (B, T)), "hw": self._buf("hwtk", (B, T, 3, E)),
+                "qv": self._buf("qvtk", (B, T, A)), "xout": self._buf("xotk", (B, T, A + 3, E)), "xmid": None}
+        return ops.mixer_unroll_fwd(self.sm, self.pack_mt, state, h_tg, qmode_on=1, q_on=q_tg, actions=act, T_on=T,
+                                    timer=self.timer, outs=(o_tk, None))
+
     def _log_stats(self, t_env, td, qtot, term, filled):
         """The NQLearner log values, when one is due: one library launch (the masked
         fp64 sums of |td|, Qtot and the targets, t2o_td_stats) beside two small copies
@@ -479,11 +561,15 @@ class TDLearner:
         self.log_stats_t = t_env
 
     def _finish(self, episode_num, td, o_on, t_env=0, term=None, filled=None):
-        # 7. clip + Adam
+        # 7. clip + Adam (or RMSprop)
         self.step_count += 1
-        ops.adam_step(self.params, self.grad[:-1], self.exp_avg, self.exp_avg_sq, self.step_count, lr=self.lr,
-                      betas=self.betas, eps=self.eps, weight_decay=self.wd, max_grad_norm=self.clip,
-                      workspace=self.adam_ws, grad_div=self.grad[-1:], grad_norm_out=self.grad_norm)
+        opt_kw = dict(lr=self.lr, eps=self.eps, weight_decay=self.wd, max_grad_norm=self.clip, workspace=self.adam_ws,
+                      grad_div=self.grad[-1:], grad_norm_out=self.grad_norm)
+        if self.optimizer == "rmsprop":
+            ops.rmsprop_step(self.params, self.grad[:-1], self.exp_avg_sq, alpha=self.alpha, **opt_kw)
+        else:
+            ops.adam_step(self.params, self.grad[:-1], self.exp_avg, self.exp_avg_sq, self.step_count,
+                          betas=self.betas, **opt_kw)
         self._params_written()
         if self.logger is not None and t_env - self.log_stats_t >= self.learner_log_interval:
             self._log_stats(t_env, td, o_on["y"], term, filled)
@@ -494,6 +580,8 @@ class TDLearner:
         info = {"td_errors_abs": prio.cpu() if self.priorities_to_cpu else prio,
                 "loss_sum": td["loss"][0:1], "mask_sum": td["loss"][1:2], "grad_norm": self.grad_norm,
                 "qtot": o_on["y"], "targets": td["targets"]}
+        if self.q_lambda:  # what t2o_td_qlambda read: [B, T] and the target mix [B, T+1]
+            info["qtot_taken"], info["qtot_tgt"] = td["qtot_taken"], td["qtot_tgt"]
         return info
 
 

@@ -9,8 +9,8 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from ._lib import (AgentBwdArgs, AgentFwdArgs, MixerBwdArgs, MixerFwdArgs, TapeArgs, TDArgs, check, lib, ptr,
-                   stream_ptr)
+from ._lib import (AgentBwdArgs, AgentFwdArgs, MixerBwdArgs, MixerFwdArgs, TapeArgs, TDArgs, TDQLambdaArgs, check, lib,
+                   ptr, stream_ptr)
 
 AGENT, MIXER = 0, 1
 
@@ -486,15 +486,9 @@ def _mask_dtype(t):
 TD_ALGOS = {"auto": 0, "sequential": 1, "wave": 2}  # include/t2omca.h T2O_TD_*
 
 
-def td_loss(qtot, qtot_tgt, reward, terminated=None, filled=None, per_weight=None, gamma=0.99,
-            td_lambda=0.6, mask_sum=0.0, algo="auto", mask_sum_acc=None):
-    """TD(λ) targets / loss / grads / priorities (PyMARL2 NQLearner contract).
-    qtot [B,T], qtot_tgt [B,T+1]; reward [B, >=T] float view; terminated / filled
-    [B, >=T] views in float32, uint8/bool, int32 or int64 (read in place).
-    algo: "sequential" (the reference's backward order, one thread per episode),
-    "wave" (one wave per episode, suffix scan) or "auto" (the library default).
-    mask_sum_acc: optional 1-float device tensor that receives += Σ mask.
-    Returns dict(gq [B,T], targets [B,T], prio [B], loss [2])."""
+def _td_call(what, args_cls, qtot, qtot_tgt, reward, terminated, filled, per_weight, gamma, td_lambda, mask_sum,
+             algo, mask_sum_acc, **extra):
+    """The host checks, outputs and argument struct td_loss and td_qlambda share."""
     _dev(qtot, qtot_tgt, reward, per_weight, mask_sum_acc)
     for m in (terminated, filled):  # any mask dtype of _MASK_DT, device-resident
         if m is not None and not m.is_cuda:
@@ -506,14 +500,49 @@ def td_loss(qtot, qtot_tgt, reward, terminated=None, filled=None, per_weight=Non
     out = dict(gq=torch.empty(B, T, device=dev), targets=torch.empty(B, T, device=dev),
                prio=torch.empty(B, device=dev), loss=torch.empty(2, device=dev))
     rs, ts, fs = _mstrides(reward), _mstrides(terminated), _mstrides(filled)
-    a = TDArgs(qtot=_p(qtot), qtot_tgt=_p(qtot_tgt), reward=_p(reward), rw_sb=rs[0], rw_st=rs[1],
-               term=_p(terminated), tm_sb=ts[0], tm_st=ts[1], filled=_p(filled), fl_sb=fs[0], fl_st=fs[1],
-               per_weight=_p(per_weight), gq=_p(out["gq"]), targets=_p(out["targets"]), prio=_p(out["prio"]),
-               loss=_p(out["loss"]), mask_sum_acc=_p(mask_sum_acc), gamma=float(gamma), td_lambda=float(td_lambda),
-               mask_sum=float(mask_sum), term_dtype=_mask_dtype(terminated), filled_dtype=_mask_dtype(filled),
-               algo=TD_ALGOS[algo], B=B, T=T)
-    check(lib().t2o_td_loss(ctypes.byref(a), stream_ptr()), "td_loss")
+    a = args_cls(qtot=_p(qtot), qtot_tgt=_p(qtot_tgt), reward=_p(reward), rw_sb=rs[0], rw_st=rs[1],
+                 term=_p(terminated), tm_sb=ts[0], tm_st=ts[1], filled=_p(filled), fl_sb=fs[0], fl_st=fs[1],
+                 per_weight=_p(per_weight), gq=_p(out["gq"]), targets=_p(out["targets"]), prio=_p(out["prio"]),
+                 loss=_p(out["loss"]), mask_sum_acc=_p(mask_sum_acc), gamma=float(gamma), td_lambda=float(td_lambda),
+                 mask_sum=float(mask_sum), term_dtype=_mask_dtype(terminated), filled_dtype=_mask_dtype(filled),
+                 algo=TD_ALGOS[algo], B=B, T=T, **extra)
+    check(getattr(lib(), "t2o_" + what)(ctypes.byref(a), stream_ptr()), what)
     return out
+
+
+def td_loss(qtot, qtot_tgt, reward, terminated=None, filled=None, per_weight=None, gamma=0.99,
+            td_lambda=0.6, mask_sum=0.0, algo="auto", mask_sum_acc=None):
+    """TD(λ) targets / loss / grads / priorities (PyMARL2 NQLearner contract).
+    qtot [B,T], qtot_tgt [B,T+1]; reward [B, >=T] float view; terminated / filled
+    [B, >=T] views in float32, uint8/bool, int32 or int64 (read in place).
+    algo: "sequential" (the reference's backward order, one thread per episode),
+    "wave" (one wave per episode, suffix scan) or "auto" (the library default).
+    mask_sum_acc: optional 1-float device tensor that receives += Σ mask.
+    Returns dict(gq [B,T], targets [B,T], prio [B], loss [2])."""
+    return _td_call("td_loss", TDArgs, qtot, qtot_tgt, reward, terminated, filled, per_weight, gamma, td_lambda,
+                    mask_sum, algo, mask_sum_acc)
+
+
+def td_qlambda(qtot, qtot_tgt, qtot_taken, reward, terminated=None, filled=None, per_weight=None, gamma=0.99,
+               td_lambda=0.6, mask_sum=0.0, algo="auto", mask_sum_acc=None):
+    """td_loss with Peng's Q(λ) targets (include/t2omca.h t2o_td_qlambda; PyMARL2
+    NQLearner with q_lambda: True): qtot_taken [B, T] or [B, T+1] (a view with any
+    row stride, unit inner stride; steps 0..T-1 are read) is the target mixer's
+    output on the target Q of the taken actions, and each step's reward gains
+    qtot_tgt[t] - qtot_taken[t].  Everything else, the returned dict included, as
+    td_loss; the sequential kernel takes T <= 4095."""
+    _dev(qtot_taken)
+    B, T = qtot.shape
+    if qtot_taken.dim() != 2 or qtot_taken.shape[0] != B or qtot_taken.shape[1] not in (T, T + 1):
+        raise ValueError(f"td_qlambda: qtot_taken must be [{B}, {T}] or [{B}, {T + 1}], got {tuple(qtot_taken.shape)}")
+    if qtot_taken.dtype != torch.float32:
+        raise TypeError(f"td_qlambda: qtot_taken must be float32, got {qtot_taken.dtype}")
+    if qtot_taken.stride(1) != 1 or (B > 1 and qtot_taken.stride(0) < T):
+        raise ValueError(f"td_qlambda: qtot_taken needs a unit inner stride and rows that do not overlap, got "
+                         f"strides {tuple(qtot_taken.stride())}")
+    qk_sb = qtot_taken.stride(0) if B > 1 else max(qtot_taken.stride(0), T)
+    return _td_call("td_qlambda", TDQLambdaArgs, qtot, qtot_tgt, reward, terminated, filled, per_weight, gamma,
+                    td_lambda, mask_sum, algo, mask_sum_acc, qtot_taken=_p(qtot_taken), qk_sb=qk_sb)
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, step, *, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -529,6 +558,19 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, step, *, lr=1e-3, betas=(0.9, 
                               float(weight_decay), float(max_grad_norm), int(step), ptr(grad_div),
                               ptr(grad_norm_out),
                               stream_ptr()), "adam_step")
+
+
+def rmsprop_step(params, grads, square_avg, *, lr=1e-3, alpha=0.99, eps=1e-8, weight_decay=0.0, max_grad_norm=10.0,
+                 workspace=None, grad_div=None, grad_norm_out=None):
+    """In-place clip_grad_norm_ + RMSprop (torch.optim.RMSprop, momentum 0, not
+    centered) on flat fp32 buffers; clip, grad_div and grad_norm_out as adam_step."""
+    _dev(params, grads, square_avg, workspace, grad_div, grad_norm_out)
+    n = params.numel()
+    if workspace is None:
+        workspace = torch.empty(int(lib().t2o_adam_workspace_floats()), device=params.device)
+    check(lib().t2o_rmsprop_step(ptr(params), ptr(grads), ptr(square_avg), ptr(workspace), n, float(lr),
+                                 float(alpha), float(eps), float(weight_decay), float(max_grad_norm), ptr(grad_div),
+                                 ptr(grad_norm_out), stream_ptr()), "rmsprop_step")
 
 
 def select_actions(q, avail, epsilon=0.0, seed=0, counter=0, out=None):
