@@ -22,6 +22,7 @@
  *   t2o_adam_step          optimiser step with global-norm clipping
  *   t2o_td_qlambda         t2o_td_loss with Peng's Q(λ) targets (q_lambda: True)
  *   t2o_rmsprop_step       the RMSprop optimiser step (optimizer != 'adam')
+ *   t2o_noise_normal / t2o_noisy_head_*  the NoisyLinear Q head (action_selector: noisy-new)
  *   t2o_env_step / reset   MultiAgvOffloadingEnv.step/reset/get_obs/get_state
  *                          (environment_multi_mec.py:184-366, normalization.py)
  *
@@ -169,6 +170,10 @@ int t2o_unpack_grads(const t2o_layout* L, const float* params, const float* gpac
 #define T2O_ARGS_TD 5
 #define T2O_ARGS_TD_STATS 6
 #define T2O_ARGS_TD_QLAMBDA 7
+#define T2O_ARGS_NOISE 8
+#define T2O_ARGS_NOISY_FWD 9
+#define T2O_ARGS_NOISY_BWD 10
+#define T2O_ARGS_NOISY_WGRAD 11
 int t2o_args_sizeof(int which); /* sizeof the T2O_ARGS_* struct, -1 for an unknown one */
 
 /* Agent unroll forward (TransformerAgent.forward over t, transf_agent.py:54-76) for
@@ -497,6 +502,105 @@ int t2o_adam_workspace_floats(void);
 int t2o_rmsprop_step(float* params, const float* grads, float* square_avg, float* workspace, int64_t n,
                      double lr, double alpha, float eps, float weight_decay, float max_grad_norm,
                      const float* grad_div, float* grad_norm_out, void* stream);
+
+/* ---- the NoisyNet Q head (t2o_noisy.hip; transf_agent.py:37-39, args.action_selector
+ * == "noisy-new": q_basic is a NoisyLinear).  utils.noisy_liner does not ship with
+ * the reference, so the layer is a DECLARED definition (parity-unpinned, DESIGN.md
+ * §5): the independent-Gaussian NoisyNet layer as PyMARL2 uses it,
+ *   q = (u_w + s_w ⊙ ε_w) h + (u_b + s_b ⊙ ε_b),  ε ~ N(0, 1) per element,
+ * u_w [NA][E], u_b [NA] the means (a plain agent's q_basic.weight / bias: the first
+ * t2o_param_count floats of a noisy agent's flat parameters are a plain agent), s_w
+ * [NA][E], s_b [NA] the sigmas, which follow them.  The head runs beside the fused
+ * agent kernels on their h output and overwrites their q; all of it is fp32 in both
+ * precisions (h is fp32; bf16 operands stop at the fused kernels).  Limits: E <= 64,
+ * NA <= 16, A <= 64.  (Added within ABI 6: nothing existing moved.)  T2O_EINVAL for a
+ * null required pointer or a bad size, before any launch; no allocation, no
+ * synchronisation, no atomics. */
+
+/* ε of steps [t0, t1) of an unroll of T steps.  Element k of step t (k = n·E + e for
+ * ε_w[n][e], k = NA·E + n for ε_b[n]) is Box–Muller on the env_spec.uniforms stream:
+ *   u1 = U(seed', env = t, draw = counter·4096 + 2k),  u2 = U(seed', t, counter·4096 + 2k + 1),
+ *   seed' = (4·seed + kind) mod 2^64,  z = sqrt(−2 ln(1 − u1)) · cos(2π u2),
+ * evaluated in fp64 and rounded once to fp32.  kind: 0 learner online, 1 learner
+ * target, 2 runner, 3 module forward; counter: the caller's call count (the learner's
+ * step_count, the runner's episode).  Limits: NA·(E+1) <= 2048, T <= 2^24,
+ * 0 <= counter < 2^28. */
+#define T2O_NOISE_LEARNER_ONLINE 0
+#define T2O_NOISE_LEARNER_TARGET 1
+#define T2O_NOISE_RUNNER 2
+#define T2O_NOISE_MODULE 3
+typedef struct {
+  float* eps_w;               /* out [T][NA][E]; rows t0 .. t1 - 1 are written */
+  float* eps_b;               /* out [T][NA] */
+  uint64_t seed;
+  int64_t counter;
+  int32_t kind;               /* T2O_NOISE_* */
+  int32_t E, NA;
+  int32_t T, t0, t1;
+} t2o_noise_args;
+int t2o_noise_normal(const t2o_noise_args* a, void* stream);
+
+/* The head of one network over steps [t0, t1): q[b][t][a][:] = W_t h[b][t][a][:] + b_t,
+ * W_t = u_w + s_w ⊙ eps_w[t], b_t = u_b + s_b ⊙ eps_b[t], written over the q the agent
+ * unroll left there.  eps_w = eps_b = NULL: the mean head (s_w / s_b unused). */
+typedef struct {
+  const float* h;             /* [b][h_ts][a][E]: the agent unroll's h */
+  const float* u_w;
+  const float* u_b;
+  const float* s_w;
+  const float* s_b;
+  const float* eps_w;         /* [>= t1][NA][E] (t2o_noise_normal's), or NULL */
+  const float* eps_b;         /* [>= t1][NA], or NULL */
+  float* q;                   /* out [b][q_ts][a][NA] */
+  int32_t h_ts, q_ts;
+  int32_t B, A, E, NA;
+  int32_t t0, t1;             /* t1 <= min(h_ts, q_ts) */
+} t2o_noisy_fwd_args;
+int t2o_noisy_head_fwd(const t2o_noisy_fwd_args* a, void* stream);
+
+/* Backward of the head at the taken actions over steps [t_lo, t_hi), any ranges in
+ * any order:
+ *   gh_out[b][t][a][:] = gh_in[b][t][a][:] + gchosen[b][t][a] · W_t[action][:]
+ *   gpart[t][p][n][0..E) = Σ over the rows (b, a) of part p with action == n of
+ *                          gchosen · h,  gpart[t][p][n][E] = Σ gchosen
+ * (P = t2o_noisy_head_parts(B, A) row parts per step, each summed in a fixed order
+ * that depends on the shape only).  gh_out is what t2o_agent_unroll_bwd takes as gh,
+ * with gchosen = gq = NULL there.  An action outside [0, NA) contributes nothing. */
+typedef struct {
+  const float* gchosen;       /* [B][T][A] dL/dq[action] */
+  const int64_t* actions;     /* [b][t][a], element strides act_sb, act_st, a-stride 1 */
+  int64_t act_sb, act_st;
+  const float* h;             /* [b][h_ts][a][E], h_ts >= T */
+  const float* u_w;
+  const float* s_w;
+  const float* eps_w;         /* as the forward's; NULL: the mean head */
+  const float* gh_in;         /* [B][T][A][E] or NULL (zeros) */
+  float* gh_out;              /* out [B][T][A][E] (may be gh_in) */
+  float* gpart;               /* out [T][P][NA][E+1] */
+  int32_t h_ts;
+  int32_t B, T, A, E, NA;
+  int32_t t_lo, t_hi;         /* t_hi <= 0: T */
+} t2o_noisy_bwd_args;
+int t2o_noisy_head_bwd(const t2o_noisy_bwd_args* a, void* stream);
+int t2o_noisy_head_parts(int B, int A); /* P above (T2O_EINVAL on a bad size) */
+
+/* After the backward has covered every step of [0, T): the head's weight gradients,
+ * accumulated (+=, as t2o_unpack_grads) into the caller's slots,
+ *   du_w, du_b += Σ_t Σ_p gpart[t][p],   ds_w, ds_b += Σ_t eps[t] ⊙ Σ_p gpart[t][p],
+ * one wave per element in a fixed order over (t, p): bit-identical run to run and
+ * whatever step ranges the backward ran in.  eps_w = eps_b = NULL: only du_*. */
+typedef struct {
+  const float* gpart;
+  const float* eps_w;
+  const float* eps_b;
+  float* du_w;                /* [NA][E] */
+  float* du_b;                /* [NA] */
+  float* ds_w;
+  float* ds_b;
+  int32_t B, T, A, E, NA;
+  int32_t reserved_;
+} t2o_noisy_wgrad_args;
+int t2o_noisy_head_wgrad(const t2o_noisy_wgrad_args* a, void* stream);
 
 /* Diagnostic: runs the cross-lane primitives the kernels rely on (4-lane
  * all-reduces via ds_bpermute and via gfx950 permlane swaps, 16-lane DPP row

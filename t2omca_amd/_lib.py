@@ -32,7 +32,8 @@ _LP = ctypes.POINTER(Layout)
 
 def _fields(spec):
     """'name:type, ...' (types P pointer, I int32, J int64, F float, L layout*) -> ctypes _fields_."""
-    ty = {"P": _P, "I": _I32, "J": _I64, "F": _F, "L": _LP, "IP": ctypes.POINTER(ctypes.c_int32)}
+    ty = {"P": _P, "I": _I32, "J": _I64, "F": _F, "L": _LP, "IP": ctypes.POINTER(ctypes.c_int32),
+          "U": ctypes.c_uint64}
     out = []
     for item in spec.split(","):
         n, t = item.strip().split(":")
@@ -82,7 +83,16 @@ TDStatsArgs = _args_class("TDStatsArgs", 6, """qtot:P, targets:P, term:P, tm_sb:
 TDQLambdaArgs = _args_class("TDQLambdaArgs", 7, """qtot:P, qtot_tgt:P, reward:P, rw_sb:J, rw_st:J, term:P, tm_sb:J,
     tm_st:J, filled:P, fl_sb:J, fl_st:J, per_weight:P, gq:P, targets:P, prio:P, loss:P, mask_sum_acc:P, gamma:F,
     td_lambda:F, mask_sum:F, term_dtype:I, filled_dtype:I, algo:I, B:I, T:I, qtot_taken:P, qk_sb:J""")
-ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs, TDQLambdaArgs)
+NoiseArgs = _args_class("NoiseArgs", 8, "eps_w:P, eps_b:P, seed:U, counter:J, kind:I, E:I, NA:I, T:I, t0:I, t1:I")
+NoisyFwdArgs = _args_class("NoisyFwdArgs", 9, """h:P, u_w:P, u_b:P, s_w:P, s_b:P, eps_w:P, eps_b:P, q:P, h_ts:I,
+    q_ts:I, B:I, A:I, E:I, NA:I, t0:I, t1:I""")
+NoisyBwdArgs = _args_class("NoisyBwdArgs", 10, """gchosen:P, actions:P, act_sb:J, act_st:J, h:P, u_w:P, s_w:P,
+    eps_w:P, gh_in:P, gh_out:P, gpart:P, h_ts:I, B:I, T:I, A:I, E:I, NA:I, t_lo:I, t_hi:I""")
+NoisyWgradArgs = _args_class("NoisyWgradArgs", 11, """gpart:P, eps_w:P, eps_b:P, du_w:P, du_b:P, ds_w:P, ds_b:P,
+    B:I, T:I, A:I, E:I, NA:I, reserved_:I""")
+ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs, TDQLambdaArgs,
+                NoiseArgs, NoisyFwdArgs, NoisyBwdArgs, NoisyWgradArgs)
+NOISE_KINDS = {"learner_online": 0, "learner_target": 1, "runner": 2, "module": 3}  # include/t2omca.h T2O_NOISE_*
 EP_STATS = 10  # include/t2omca.h T2O_EP_STATS
 
 
@@ -129,6 +139,11 @@ EXPORTS = {
     "t2o_td_qlambda": (ctypes.c_int, [ctypes.POINTER(TDQLambdaArgs), ctypes.c_void_p]),
     "t2o_rmsprop_step": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_double] * 2 +
                          [ctypes.c_float] * 3 + [ctypes.c_void_p] * 3),
+    "t2o_noise_normal": (ctypes.c_int, [ctypes.POINTER(NoiseArgs), ctypes.c_void_p]),
+    "t2o_noisy_head_fwd": (ctypes.c_int, [ctypes.POINTER(NoisyFwdArgs), ctypes.c_void_p]),
+    "t2o_noisy_head_bwd": (ctypes.c_int, [ctypes.POINTER(NoisyBwdArgs), ctypes.c_void_p]),
+    "t2o_noisy_head_parts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "t2o_noisy_head_wgrad": (ctypes.c_int, [ctypes.POINTER(NoisyWgradArgs), ctypes.c_void_p]),
     "t2o_probe_lane_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_scatter_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_xdl_hazards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -162,9 +177,14 @@ _DIAGNOSTIC = {"t2o_bf_swz", "t2o_probe_lane_ops", "t2o_probe_scatter_ops", "t2o
 # the logged statistics, the Q(λ) targets and the RMSprop step (same ABI version:
 # nothing existing moved), which a build from before them lacks; calling one on such
 # a library raises AttributeError
-_OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats", "t2o_td_qlambda", "t2o_rmsprop_step"}
+_OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats", "t2o_td_qlambda", "t2o_rmsprop_step",
+                           # ... and the NoisyNet head
+                           "t2o_noise_normal", "t2o_noisy_head_fwd", "t2o_noisy_head_bwd", "t2o_noisy_head_parts",
+                           "t2o_noisy_head_wgrad"}
 # argument structs of optional exports: no size to check where the export is absent
-_STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats", TDQLambdaArgs: "t2o_td_qlambda"}
+_STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats", TDQLambdaArgs: "t2o_td_qlambda", NoiseArgs: "t2o_noise_normal",
+                  NoisyFwdArgs: "t2o_noisy_head_fwd", NoisyBwdArgs: "t2o_noisy_head_bwd",
+                  NoisyWgradArgs: "t2o_noisy_head_wgrad"}
 
 _lib = None
 

@@ -346,6 +346,10 @@ extern "C" int t2o_args_sizeof(int which) {
     case T2O_ARGS_TD: return (int)sizeof(t2o_td_args);
     case T2O_ARGS_TD_STATS: return (int)sizeof(t2o_td_stats_args);
     case T2O_ARGS_TD_QLAMBDA: return (int)sizeof(t2o_td_qlambda_args);
+    case T2O_ARGS_NOISE: return (int)sizeof(t2o_noise_args);
+    case T2O_ARGS_NOISY_FWD: return (int)sizeof(t2o_noisy_fwd_args);
+    case T2O_ARGS_NOISY_BWD: return (int)sizeof(t2o_noisy_bwd_args);
+    case T2O_ARGS_NOISY_WGRAD: return (int)sizeof(t2o_noisy_wgrad_args);
     default: return -1;
   }
 }

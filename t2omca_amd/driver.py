@@ -24,6 +24,9 @@ test runs every test_interval env steps (:241-256); a checkpoint in a directory
 named by t_env (:265-279); ``episode += batch_size_run``; the "episode" log line
 every log_interval env steps (:283-286).  The loop ends once t_env > t_max.
 
+A NoisyNet agent (``action_selector: noisy-new``) needs nothing here: the runner and
+the learner detect it, and their noise is a function of their seeds and counters.
+
 The accumulated_episodes skip is the reference's ``continue``: it also skips the
 rest of that iteration — tests, checkpoint, the episode count and the log line.
 

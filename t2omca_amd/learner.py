@@ -30,6 +30,24 @@ priorities are copied out):
   (contract="pair": both tapes in one launch after the agent BPTT, one all-reduce)
   clip_grad_norm_ + Adam                           t2o_adam_step
   [optimizer="rmsprop": clip_grad_norm_ + RMSprop  t2o_rmsprop_step]
+
+A noisy agent (modules.TransformerAgent with action_selector "noisy-new",
+``agent.noisy``) adds the NoisyNet head's launches — a plain agent
+issues none of them:
+
+  ε of the online and the target network, T+1 steps each   t2o_noise_normal x2 (side stream,
+      (seed noise_seed, counter step_count, kinds 0 / 1)    beside the packs)
+  after the agent unroll (per step range when pipelined):
+      q_on, q_tg overwritten from h_on, h_tg               t2o_noisy_head_fwd x2
+  after the mixer BPTT (per step range when pipelined):
+      dL/dh = dL/dhidden + dL/dq_chosen · W_t[action],
+      per-step weight-gradient partials                     t2o_noisy_head_bwd
+  the agent BPTT then runs on dL/dh alone (no q gradient: the fused head adds zeros
+  to q_basic's slots), and after t2o_unpack_grads
+      Σ_t partials into the u_w, u_b, s_w, s_b slots        t2o_noisy_head_wgrad
+The mixers, the TD loss and the Q(λ) taken mix read the q arrays and run unchanged.
+The head is fp32 in both precisions.  noise_seed is NOT mixed with the rank: every
+data-parallel rank draws the same network, so the shard sum is the full-batch gradient.
 """
 import dataclasses
 import os
@@ -77,7 +95,8 @@ class TDLearner:
                  target_update_interval=200, optim_betas=(0.9, 0.999), optim_eps=1e-8, weight_decay=0.0,
                  detach_mixer_hidden=False, process_group=None, priorities_to_cpu=True, precision="fp32",
                  overlap=True, td_algo="auto", contract="side", pipeline="auto", pipeline_ranges=6,
-                 logger=None, learner_log_interval=10000, q_lambda=False, optimizer="adam", optim_alpha=0.99):
+                 logger=None, learner_log_interval=10000, q_lambda=False, optimizer="adam", optim_alpha=0.99,
+                 noise_seed=0):
         # options first (a bad value fails here, not inside the first train())
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' or 'bf16'")
@@ -107,7 +126,13 @@ class TDLearner:
         self.precision = precision
         self.sa = dataclasses.replace(agent.shape, prec=prec)
         self.sm = dataclasses.replace(mixer.shape, prec=prec)
-        self.na, self.nm = self.sa.n_params, self.sm.n_params
+        # a noisy agent's flat parameters: the plain agent's na_net floats (what the packs and
+        # the fused kernels read), then the head's NA·(E+1) sigmas
+        self.noisy = bool(getattr(agent, "noisy", False))
+        self.noise_seed = int(noise_seed)
+        self.na_net, self.nm = self.sa.n_params, self.sm.n_params
+        self.n_head = self.sa.NA * (self.sa.E + 1)
+        self.na = self.na_net + (self.n_head if self.noisy else 0)
         assert self.na == sum(p.numel() for p in agent.parameters())
         assert self.nm == sum(p.numel() for p in mixer.parameters())
         self.device = dev
@@ -181,8 +206,29 @@ class TDLearner:
         src = self.target_params if target else self.params
         return src[self.na:]
 
+    def _head_views(self, flat):
+        """(u_w [NA, E], u_b [NA], s_w, s_b) of a noisy agent's head as views of a flat
+        buffer laid out like the parameters (params, target_params, grad): the means are
+        the plain agent's last NA·(E+1) floats (q_basic.weight, bias), the sigmas follow."""
+        NA, E = self.sa.NA, self.sa.E
+        o, n = self.na_net - self.n_head, self.na_net
+        return (flat[o:o + NA * E].view(NA, E), flat[o + NA * E:n],
+                flat[n:n + NA * E].view(NA, E), flat[n + NA * E:n + self.n_head])
+
+    def _draw_noise(self, T1):
+        """ε of this update's online and target network (kinds 0 / 1, counter step_count:
+        a function of the seeds and the step alone, so a resumed run draws the same),
+        two launches on the current stream into buffers the learner keeps."""
+        NA, E = self.sa.NA, self.sa.E
+        out = []
+        for name, kind in (("on", "learner_online"), ("tg", "learner_target")):
+            eps = (self._buf("eps_w_" + name, (T1, NA, E)), self._buf("eps_b_" + name, (T1, NA)))
+            out.append(ops.noise_normal(E, NA, T1, self.noise_seed, kind, self.step_count, out=eps))
+        self.last_noise = tuple(out)  # (online, target), each (eps_w [T+1, NA, E], eps_b [T+1, NA])
+        return self.last_noise
+
     def _pack_targets(self):
-        ops.pack_params(self.sa, self.target_params[:self.na], self.pack_at)
+        ops.pack_params(self.sa, self.target_params[:self.na_net], self.pack_at)
         ops.pack_params(self.sm, self.target_params[self.na:], self.pack_mt)
 
     def update_targets(self):
@@ -257,7 +303,11 @@ class TDLearner:
         """Inverse of save_models; also takes checkpoints written by the reference
         framework.  As PyMARL2's NQLearner does, the target agent is reloaded from
         agent.th and the target mixer is left as it is; opt.th is optional, and one
-        written by the other optimiser is a ValueError naming both."""
+        written by the other optimiser is a ValueError naming both.  opt.th follows the
+        modules' parameter order (a noisy agent: q_basic.u_w, u_b, s_w, s_b last of the
+        agent's); an agent.th of the other head, or an opt.th whose per-parameter shapes
+        are not these modules', is a ValueError that says so.  Every check comes before
+        anything is overwritten."""
         def load(name):
             return torch.load(os.path.join(path, name), map_location=self.device, weights_only=True)
         saved = load("opt.th") if os.path.exists(os.path.join(path, "opt.th")) else None
@@ -265,8 +315,26 @@ class TDLearner:
         if held is not None and held != self.optimizer:  # (before anything is overwritten)
             raise ValueError(f"opt.th holds the state of a {OPTIMIZERS[held]} optimiser, this learner runs "
                              f"{OPTIMIZERS[self.optimizer]} (optimizer={self.optimizer!r})")
+        agent_sd = load("agent.th")
+        if ("q_basic.u_w" in agent_sd) != self.noisy:
+            kinds = ("a NoisyLinear (noisy-new)", "a plain Linear")
+            raise ValueError(f"agent.th holds {kinds['q_basic.u_w' not in agent_sd]} q_basic head, this learner's "
+                             f"agent has {kinds[self.noisy]} one (noisy={self.noisy})")
+        if saved is not None:
+            params = list(self.agent.parameters()) + list(self.mixer.parameters())
+            ids = [i for g in saved.get("param_groups", []) for i in g["params"]]
+            if len(ids) != len(params):
+                raise ValueError(f"opt.th holds the state of {len(ids)} parameters, this learner's modules have "
+                                 f"{len(params)} (a checkpoint of another network or head?)")
+            for n, (i, p) in enumerate(zip(ids, params)):
+                for name, _ in self._moments():
+                    st = saved.get("state", {}).get(i)
+                    if st and name in st and tuple(st[name].shape) != tuple(p.shape):
+                        raise ValueError(f"opt.th: {name} of parameter {n} is {tuple(st[name].shape)}, this "
+                                         f"learner's parameter {n} is {tuple(p.shape)}: its per-parameter shapes "
+                                         f"do not match these modules' parameter order")
         with torch.no_grad():
-            self.agent.load_state_dict(load("agent.th"))  # copies into the flat-buffer views
+            self.agent.load_state_dict(agent_sd)  # copies into the flat-buffer views
             self.mixer.load_state_dict(load("mixer.th"))
             self.target_params[:self.na].copy_(self.params[:self.na])
         if saved is None:
@@ -304,7 +372,10 @@ class TDLearner:
                 "log_stats_t": int(self.log_stats_t),
                 # (optim_alpha as a 0-d fp64 tensor: every value here is a tensor, an int or a str)
                 "q_lambda": self.q_lambda, "optimizer": self.optimizer,
-                "optim_alpha": torch.tensor(self.alpha, dtype=torch.float64)}
+                "optim_alpha": torch.tensor(self.alpha, dtype=torch.float64),
+                # the NoisyNet head: with it `na` covers the sigmas; its noise is a function of
+                # noise_seed and step_count alone, so no further state
+                "noisy": self.noisy, "noise_seed": self.noise_seed}
 
     def load_state_dict(self, sd):
         """In place into the flat buffers, which the modules' parameters view; then
@@ -312,10 +383,13 @@ class TDLearner:
         data-parallel ranks aligned (a collective with a process group).  ValueError
         naming the field when the parameter counts, the precision, the targets
         (q_lambda) or the optimiser differ; a state saved before the last three
-        existed holds their defaults."""
-        sd = {"q_lambda": False, "optimizer": "adam", "optim_alpha": 0.99, **sd}
+        existed holds their defaults.  Likewise `noisy` (a state saved before it
+        existed is a plain agent's), and with a noisy agent `noise_seed`."""
+        sd = {"q_lambda": False, "optimizer": "adam", "optim_alpha": 0.99, "noisy": False, "noise_seed": 0, **sd}
         sd["optim_alpha"] = float(sd["optim_alpha"])
-        check_fields("TDLearner", sd, {"format": 1, "na": self.na, "nm": self.nm, "precision": self.precision,
+        # (noisy before na: a noisy state in a plain learner is told by its name, not by its size)
+        head = {"noisy": self.noisy, **({"noise_seed": self.noise_seed} if self.noisy else {})}
+        check_fields("TDLearner", sd, {"format": 1, **head, "na": self.na, "nm": self.nm, "precision": self.precision,
                                        "q_lambda": self.q_lambda, "optimizer": self.optimizer,
                                        "optim_alpha": self.alpha})
         with torch.no_grad():
@@ -391,10 +465,13 @@ class TDLearner:
         side = self._side_stream() if self.overlap else main
         side.wait_stream(main)
         with torch.cuda.stream(side):
+            if self.noisy:  # both networks' ε, beside the packs (main waits before the first head launch)
+                eps_on, eps_tg = self._draw_noise(T1)
+                noise_drawn = side.record_event()
             self.grad.zero_()
             ops.pack_params(self.sm, self.params[self.na:], self.pack_m)  # beside the agent's pack + forward
             mixer_packed = side.record_event()  # (main waits for it before the mixer: grad is clear by then too)
-        ops.pack_params(self.sa, self.params[:self.na], self.pack_a)
+        ops.pack_params(self.sa, self.params[:self.na_net], self.pack_a)
         hmid = self._buf("hmid", (B, T1, self.sa.D - 1, A, self.sa.E)) if self.sa.D > 1 else None
         piped = self._pipelined(B) and side is not main
         if self.pipeline is True and not piped:
@@ -419,8 +496,13 @@ class TDLearner:
                                             hmid_on=hmid, outs=(q_on, h_on, q_tg, h_tg), launcher=True)
             mixer_go = ops.mixer_unroll_fwd(self.sm, self.pack_m, state, h_on, q_on=q_on, hid_tg=h_tg, q_tg=q_tg,
                                             outs=(o_on, o_tg), launcher=True, **mixer_kw)
+            if self.noisy:
+                main.wait_event(noise_drawn)
+                heads_go = self._head_fwd(q_on, h_on, q_tg, h_tg, eps_on, eps_tg, launcher=True)
             for t0, t1 in self._ranges(T1):
                 agent_go(t0, t1)
+                if self.noisy:  # the range's q from its h, before the mixer may read them
+                    heads_go(t0, t1)
                 agent_done = main.record_event()
                 with torch.cuda.stream(side):
                     side.wait_event(agent_done)
@@ -436,6 +518,9 @@ class TDLearner:
             # 1. agents: online + target over t = 0..T
             q_on, h_on, q_tg, h_tg = ops.agent_unroll_fwd(self.sa, self.pack_a, obs, pack_tg=self.pack_at,
                                                           timer=self.timer, hmid_on=hmid)
+            if self.noisy:  # the noisy head's q over the fused (mean-head) q, both networks
+                main.wait_event(noise_drawn)
+                self._head_fwd(q_on, h_on, q_tg, h_tg, eps_on, eps_tg)
             # 2. mixers: online on chosen Q (t < T), target on double-Q (t <= T)
             main.wait_event(mixer_packed)
             o_on, o_tg = ops.mixer_unroll_fwd(self.sm, self.pack_m, state, h_on, q_on=q_on, hid_tg=h_tg, q_tg=q_tg,
@@ -473,8 +558,14 @@ class TDLearner:
             mixer_go = ops.mixer_unroll_bwd(self.sm, self.pack_m, state, h_on, o_on, td["gq"], slabs=slabs_m,
                                             timer=self.timer, tape=tape_m, work=work_m, outs=(gqv, ghid),
                                             carry=carry_m, launcher=True)
-            agent_go, _ = ops.agent_unroll_bwd(self.sa, self.pack_a, obs, h_on, gchosen=gqv, actions=act,
-                                               gh=None if self.detach_mixer_hidden else ghid, slabs=slabs_a,
+            gh, gchosen, head_go = None if self.detach_mixer_hidden else ghid, gqv, None
+            if self.noisy:
+                # the head's backward turns each range's dL/dq_chosen (+ dL/dhidden) into the
+                # dL/dh the agent BPTT runs on alone
+                head_go, gh, gpart = self._head_bwd(gqv, act, h_on, eps_on, gh, launcher=True)
+                gchosen = None
+            agent_go, _ = ops.agent_unroll_bwd(self.sa, self.pack_a, obs, h_on, gchosen=gchosen, actions=act,
+                                               gh=gh, slabs=slabs_a,
                                                timer=self.timer, hmid=hmid, tape=tape_a, gcarry=carry_a,
                                                launcher=True)
             side.wait_stream(main)
@@ -485,13 +576,17 @@ class TDLearner:
                     mixer_go(2, t_lo, t_hi)
                     mixer_done = side.record_event()
                 main.wait_event(mixer_done)
+                if head_go is not None:
+                    head_go(t_lo, t_hi)
                 contract_a = agent_go(t_lo, t_hi)
             with torch.cuda.stream(side):
                 gm = contract_m()
                 ops.unpack_grads(self.sm, self.params[self.na:], gm, self.grad[self.na:self.na + self.nm])
                 work_m_ = allreduce_async(self.grad[self.na:], self.pg)
             ga = contract_a()
-            ops.unpack_grads(self.sa, self.params[:self.na], ga, self.grad[:self.na])
+            ops.unpack_grads(self.sa, self.params[:self.na_net], ga, self.grad[:self.na_net])
+            if self.noisy:
+                self._head_wgrad(gpart, B, A, eps_on)
             work_a = allreduce_async(self.grad[:self.na], self.pg)
             main.wait_stream(side)
             wait_all((work_m_, work_a))
@@ -501,6 +596,11 @@ class TDLearner:
                                                         slabs=slabs_m, timer=self.timer, tape=tape_m,
                                                         defer_contract=True, work=work_m)
         gh = None if self.detach_mixer_hidden else ghid
+        if self.noisy:
+            # 4b. the head's backward: dL/dh = dL/dhidden + dL/dq_chosen · W_t[action]; the agent
+            #     BPTT then takes no q gradient (its fused head adds zeros to q_basic's slots)
+            gh, gpart = self._head_bwd(gqv, act, h_on, eps_on, gh)
+            gqv = None
         if self.contract == "pair":
             # 5. agent BPTT (grads of the chosen Q and, unless detached, of the hidden
             #    states), then both tapes contracted in one launch
@@ -511,7 +611,9 @@ class TDLearner:
             # 6. grads in reference parameter order; data parallel: one all-reduce of
             #    [agent grads, mixer grads, Σ mask] (336 KB at the default network)
             ops.unpack_grads(self.sm, self.params[self.na:], gm, self.grad[self.na:self.na + self.nm])
-            ops.unpack_grads(self.sa, self.params[:self.na], ga, self.grad[:self.na])
+            ops.unpack_grads(self.sa, self.params[:self.na_net], ga, self.grad[:self.na_net])
+            if self.noisy:
+                self._head_wgrad(gpart, B, A, eps_on)
             wait_all((allreduce_async(self.grad, self.pg),))
         else:
             side.wait_stream(main)
@@ -521,7 +623,9 @@ class TDLearner:
                 work_m = allreduce_async(self.grad[self.na:], self.pg)
             ga, _ = ops.agent_unroll_bwd(self.sa, self.pack_a, obs, h_on, gchosen=gqv, actions=act, gh=gh,
                                          slabs=slabs_a, timer=self.timer, hmid=hmid, tape=tape_a)
-            ops.unpack_grads(self.sa, self.params[:self.na], ga, self.grad[:self.na])
+            ops.unpack_grads(self.sa, self.params[:self.na_net], ga, self.grad[:self.na_net])
+            if self.noisy:
+                self._head_wgrad(gpart, B, A, eps_on)
             work_a = allreduce_async(self.grad[:self.na], self.pg)
             main.wait_stream(side)
             wait_all((work_m, work_a))
@@ -538,6 +642,38 @@ class TDLearner:
                 "qv": self._buf("qvtk", (B, T, A)), "xout": self._buf("xotk", (B, T, A + 3, E)), "xmid": None}
         return ops.mixer_unroll_fwd(self.sm, self.pack_mt, state, h_tg, qmode_on=1, q_on=q_tg, actions=act, T_on=T,
                                     timer=self.timer, outs=(o_tk, None))
+
+    def _head_fwd(self, q_on, h_on, q_tg, h_tg, eps_on, eps_tg, launcher=False):
+        """The noisy head of both networks on the current stream: q_on / q_tg overwritten
+        from h_on / h_tg (one launch per network).  launcher: go(t0, t1) per step range."""
+        gos = []
+        for q, h, eps, flat in ((q_on, h_on, eps_on, self.params), (q_tg, h_tg, eps_tg, self.target_params)):
+            u_w, u_b, s_w, s_b = self._head_views(flat)
+            gos.append(ops.noisy_head_fwd(h, q, u_w, u_b, s_w, s_b, eps=eps, timer=self.timer, launcher=True))
+
+        def go(t0, t1):
+            for g in gos:
+                g(t0, t1)
+        if launcher:
+            return go
+        go(0, q_on.shape[1])
+
+    def _head_bwd(self, gqv, act, h_on, eps_on, gh_in, launcher=False):
+        """The online head's backward (t2o_noisy_head_bwd) into buffers the learner keeps:
+        returns (gh_out [B, T, A, E], gpart), with launcher first go(t_lo, t_hi)."""
+        B, T, A = gqv.shape
+        u_w, _, s_w, _ = self._head_views(self.params)
+        gh_out = self._buf("gh_head", (B, T, A, self.sa.E))
+        gpart = self._buf("gpart_head", (T, ops.noisy_head_parts(B, A), self.sa.NA, self.sa.E + 1))
+        out = ops.noisy_head_bwd(gqv, act, h_on, u_w, s_w, eps_on[0], gh_in=gh_in, gh_out=gh_out, gpart=gpart,
+                                 timer=self.timer, launcher=launcher)
+        return out
+
+    def _head_wgrad(self, gpart, B, A, eps_on):
+        """Σ_t of the head's partials into its four slots of the flat gradient (+=, after
+        t2o_unpack_grads left zeros in q_basic's slots)."""
+        du_w, du_b, ds_w, ds_b = self._head_views(self.grad)
+        ops.noisy_head_wgrad(gpart, B, A, du_w, du_b, ds_w, ds_b, eps=eps_on, timer=self.timer)
 
     def _log_stats(self, t_env, td, qtot, term, filled):
         """The NQLearner log values, when one is due: one library launch (the masked

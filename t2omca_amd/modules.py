@@ -84,7 +84,8 @@ class _PackCache:
         if key != self.key:
             with torch.no_grad():
                 flat = torch.cat([p.detach().reshape(-1) for p in params])
-            self.flat, self.pack = flat, ops.pack_params(shape, flat)
+            # (a noisy agent's sigmas follow the plain agent's parameters: the pack reads the prefix)
+            self.flat, self.pack = flat, ops.pack_params(shape, flat[:shape.n_params])
             self.key = key
             self.rebuilds += 1
         return params, self.flat, self.pack
@@ -144,8 +145,74 @@ class _AgentStep(torch.autograd.Function):
         return (None, None, None, None, gh0.view(b, a, shape.E)) + _split_like(gflat, ctx.param_shapes)
 
 
+class NoisyLinear(nn.Module):
+    """Parameter container of the NoisyNet head (transf_agent.py:37-39 builds
+    ``NoisyLinear(emb, n_actions)`` from utils.noisy_liner, which does not ship with
+    the reference; this is the DECLARED definition of DESIGN.md §5, the
+    independent-Gaussian layer as PyMARL2 uses it):
+
+        training:  q = (u_w + s_w ⊙ ε_w) h + (u_b + s_b ⊙ ε_b),  ε ~ N(0, 1), fresh per call
+        eval:      q = u_w h + u_b
+
+    The means take nn.Linear's default initialisation, the sigmas are 0.017.
+    Registered in the order u_w, u_b, s_w, s_b: an agent's flat parameters are then a
+    plain agent's (q_basic.weight = u_w, q_basic.bias = u_b) followed by the sigmas."""
+
+    SIGMA_INIT = 0.017
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        if not bias:
+            raise ValueError("t2omca_amd: NoisyLinear is built with a bias (transf_agent.py:38)")
+        self.in_features, self.out_features = in_features, out_features
+        lin = nn.Linear(in_features, out_features)  # its default initialisation, its random draws
+        self.u_w = nn.Parameter(lin.weight.detach().clone())
+        self.u_b = nn.Parameter(lin.bias.detach().clone())
+        self.s_w = nn.Parameter(torch.full((out_features, in_features), self.SIGMA_INIT))
+        self.s_b = nn.Parameter(torch.full((out_features,), self.SIGMA_INIT))
+
+
+class _NoisyHead(torch.autograd.Function):
+    """The noisy head of one step on the HIP kernels (t2o_noisy_head_*): gradients to
+    h and the four parameters.  The backward kernel works on one action's gradient per
+    row (the learner's chosen-Q form), so a full dL/dq runs it once per action, each
+    pass adding to dL/dh and to the weight-gradient sums."""
+
+    @staticmethod
+    def forward(ctx, h, u_w, u_b, s_w, s_b, eps_w, eps_b):
+        b, a, E = h.shape
+        h4 = h.detach().contiguous().view(b, 1, a, E)
+        pw = [p.detach().contiguous() for p in (u_w, u_b, s_w, s_b)]
+        q = torch.empty(b, 1, a, u_w.shape[0], device=h.device)
+        ops.noisy_head_fwd(h4, q, pw[0], pw[1], pw[2], pw[3], eps=(eps_w, eps_b))
+        ctx.save_for_backward(h4, pw[0], pw[2], eps_w, eps_b)
+        return q[:, 0]
+
+    @staticmethod
+    def backward(ctx, gq):
+        h4, u_w, s_w, eps_w, eps_b = ctx.saved_tensors
+        b, _, a, E = h4.shape
+        NA = u_w.shape[0]
+        gq = gq.contiguous()
+        gh = gpart = None
+        g = [torch.zeros_like(u_w), torch.zeros(NA, device=u_w.device),
+             torch.zeros_like(u_w), torch.zeros(NA, device=u_w.device)]
+        for n in range(NA):
+            act = torch.full((b, 1, a), n, dtype=torch.int64, device=h4.device)
+            gh, gpart = ops.noisy_head_bwd(gq[:, :, n].contiguous().view(b, 1, a), act, h4, u_w, s_w, eps_w,
+                                           gh_in=gh, gh_out=gh, gpart=gpart)
+            ops.noisy_head_wgrad(gpart, b, a, g[0], g[1], g[2], g[3], eps=(eps_w, eps_b))
+        return gh[:, 0], g[0], g[1], g[2], g[3], None, None
+
+
 class TransformerAgent(nn.Module):
-    """transf_agent.py:8-76 drop-in (HIP forward/backward)."""
+    """transf_agent.py:8-76 drop-in (HIP forward/backward).
+
+    ``args.action_selector == "noisy-new"`` builds the NoisyLinear head
+    (transf_agent.py:37-39): ``noisy`` is then True, and a training-mode forward draws
+    fresh noise (counter-based: seed ``noise_seed`` = args.noise_seed or 0, kind
+    "module", counter ``noise_calls``, which it increments) and runs the head on the
+    noisy-head kernels; an eval-mode forward is the mean head, the fused path."""
 
     def __init__(self, input_shape, args):
         super().__init__()
@@ -156,10 +223,13 @@ class TransformerAgent(nn.Module):
         self.emb_dim = args.emb
         self.feat_embedding = nn.Linear(self.feat_dim, self.emb_dim)
         self.transformer = Transformer(args.emb, args.heads, args.depth, args.ff_hidden_mult, args.dropout)
-        if getattr(self.args, "action_selector", None) == "noisy-new":
-            raise NotImplementedError("t2omca_amd: the NoisyLinear head (transf_agent.py:37-39) is not on "
-                                      "the fused path")
-        self.q_basic = nn.Linear(args.emb, args.n_actions)
+        self.noisy = getattr(self.args, "action_selector", None) == "noisy-new"
+        self.noise_seed = int(getattr(self.args, "noise_seed", 0))
+        self.noise_calls = 0  # training-mode forwards so far: the next one's noise counter
+        if self.noisy:
+            self.q_basic = NoisyLinear(args.emb, args.n_actions)
+        else:
+            self.q_basic = nn.Linear(args.emb, args.n_actions)
         self.shape = ops.NetShape(ops.AGENT, args.emb, args.heads, args.depth, self.feat_dim, args.n_actions,
                                   args.ff_hidden_mult * args.emb, self.n_entities)
         self._pack_cache = _PackCache()
@@ -173,6 +243,13 @@ class TransformerAgent(nn.Module):
             hidden_state = hidden_state.expand(b, a, self.emb_dim)
         params, flat, pack = self._pack_cache.get(self, self.shape)
         q, h = _AgentStep.apply(self.shape, flat, pack, inputs, hidden_state, *params)
+        if self.noisy and self.training:
+            # the fused step's q (the mean head) is unused; h carries the gradient
+            nl = self.q_basic
+            eps_w, eps_b = ops.noise_normal(self.emb_dim, nl.out_features, 1, self.noise_seed, "module",
+                                            self.noise_calls, device=h.device)
+            self.noise_calls += 1
+            q = _NoisyHead.apply(h, nl.u_w, nl.u_b, nl.s_w, nl.s_b, eps_w, eps_b)
         return q.view(b, a, -1), h.view(b, a, -1)
 
 

@@ -573,6 +573,145 @@ def rmsprop_step(params, grads, square_avg, *, lr=1e-3, alpha=0.99, eps=1e-8, we
                                  ptr(grad_norm_out), stream_ptr()), "rmsprop_step")
 
 
+# ---- the NoisyNet Q head (include/t2omca.h t2o_noise_normal / t2o_noisy_head_*) ----
+
+def _f32c(name, t, shape=None):
+    if not t.is_cuda:
+        raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise TypeError(f"{name}: expected a dense float32 tensor" + (f" of shape {tuple(shape)}" if shape else "") +
+                        f", got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def noise_normal(E, NA, T, seed, kind, counter, device=None, out=None, steps=None):
+    """The ε block of a noisy head (t2o_noise_normal): eps_w [T, NA, E], eps_b [T, NA],
+    one launch; kind one of _lib.NOISE_KINDS (or its number), counter the caller's
+    call count.  steps=(t0, t1) writes only those rows of `out`=(eps_w, eps_b)."""
+    if out is None:
+        out = (torch.empty(T, NA, E, device=device), torch.empty(T, NA, device=device))
+    eps_w, eps_b = out
+    _f32c("noise_normal: eps_w", eps_w, (T, NA, E))
+    _f32c("noise_normal: eps_b", eps_b, (T, NA))
+    t0, t1 = steps if steps is not None else (0, T)
+    a = _lib.NoiseArgs(eps_w=_p(eps_w), eps_b=_p(eps_b), seed=int(seed) & ((1 << 64) - 1), counter=int(counter),
+                       kind=_lib.NOISE_KINDS.get(kind, kind), E=E, NA=NA, T=T, t0=int(t0), t1=int(t1))
+    check(lib().t2o_noise_normal(ctypes.byref(a), stream_ptr(eps_w.device)), "noise_normal")
+    return eps_w, eps_b
+
+
+def noisy_head_fwd(h, q, u_w, u_b, s_w=None, s_b=None, eps=None, steps=None, timer=None, launcher=False):
+    """q[b, t] = (u_w + s_w ⊙ eps_w[t]) h[b, t] + (u_b + s_b ⊙ eps_b[t]) over steps
+    [t0, t1) (default: every step of q), written into q [B, q_ts, A, NA] over what the
+    agent unroll left there; h [B, h_ts, A, E] its hidden states.  eps=(eps_w, eps_b)
+    (noise_normal's) or None: the mean head."""
+    B, h_ts, A, E = h.shape
+    q_ts, NA = q.shape[1], q.shape[3]
+    _f32c("noisy_head_fwd: h", h)
+    _f32c("noisy_head_fwd: q", q, (B, q_ts, A, NA))
+    _f32c("noisy_head_fwd: u_w", u_w, (NA, E))
+    _f32c("noisy_head_fwd: u_b", u_b, (NA,))
+    eps_w = eps_b = None
+    if eps is not None:
+        eps_w, eps_b = eps
+        _f32c("noisy_head_fwd: s_w", s_w, (NA, E))
+        _f32c("noisy_head_fwd: s_b", s_b, (NA,))
+        _f32c("noisy_head_fwd: eps_w", eps_w, (eps_w.shape[0], NA, E))
+        _f32c("noisy_head_fwd: eps_b", eps_b, (eps_w.shape[0], NA))
+    a = _lib.NoisyFwdArgs(h=_p(h), u_w=_p(u_w), u_b=_p(u_b), s_w=_p(s_w), s_b=_p(s_b), eps_w=_p(eps_w),
+                          eps_b=_p(eps_b), q=_p(q), h_ts=h_ts, q_ts=q_ts, B=B, A=A, E=E, NA=NA)
+    fn = lib().t2o_noisy_head_fwd
+    n_eps = eps_w.shape[0] if eps_w is not None else None
+
+    def go(t0, t1):
+        if n_eps is not None and t1 > n_eps:
+            raise ValueError(f"noisy_head_fwd: steps up to {t1}, the noise covers {n_eps}")
+        a.t0, a.t1 = int(t0), int(t1)
+        _mark(timer, "begin:noisy_fwd")
+        check(fn(ctypes.byref(a), stream_ptr(h.device)), "noisy_head_fwd")
+        _mark(timer, "end:noisy_fwd")
+    if launcher:
+        return go
+    go(*(steps if steps is not None else (0, min(h_ts, q_ts))))
+    return q
+
+
+def noisy_head_parts(B, A):
+    """Row parts per step of the head backward's weight-gradient partials."""
+    n = int(lib().t2o_noisy_head_parts(int(B), int(A)))
+    if n < 1:
+        raise ValueError(f"noisy_head_parts: bad shape B={B} A={A}")
+    return n
+
+
+def noisy_head_bwd(gchosen, actions, h, u_w, s_w=None, eps_w=None, gh_in=None, gh_out=None, gpart=None, steps=None,
+                   timer=None, launcher=False):
+    """Backward of the head at the taken actions over steps [t_lo, t_hi) (default all T):
+    gh_out [B, T, A, E] = gh_in + gchosen · W_t[action] and the weight-gradient
+    partials gpart [T, P, NA, E+1] of those steps (noisy_head_wgrad sums them once
+    every step is in).  gchosen [B, T, A]; actions int64 [B, >= T, A]; h [B, >= T, A, E].
+    Returns (gh_out, gpart)."""
+    B, T, A = gchosen.shape
+    E, NA = h.shape[3], u_w.shape[0]
+    _f32c("noisy_head_bwd: gchosen", gchosen)
+    _f32c("noisy_head_bwd: h", h, (B, h.shape[1], A, E))
+    _f32c("noisy_head_bwd: u_w", u_w, (NA, E))
+    if not actions.is_cuda or actions.dtype != torch.int64 or actions.stride(2) != 1 or actions.shape[1] < T:
+        raise TypeError("noisy_head_bwd: actions must be an int64 HIP tensor [B, >= T, A] with unit agent stride")
+    if eps_w is not None:
+        _f32c("noisy_head_bwd: s_w", s_w, (NA, E))
+        _f32c("noisy_head_bwd: eps_w", eps_w, (eps_w.shape[0], NA, E))
+        if eps_w.shape[0] < T:
+            raise ValueError(f"noisy_head_bwd: {T} steps, the noise covers {eps_w.shape[0]}")
+    P = noisy_head_parts(B, A)
+    if gh_out is None:
+        gh_out = torch.empty(B, T, A, E, device=h.device)
+    if gpart is None:
+        gpart = torch.empty(T, P, NA, E + 1, device=h.device)
+    _f32c("noisy_head_bwd: gh_out", gh_out, (B, T, A, E))
+    _f32c("noisy_head_bwd: gpart", gpart, (T, P, NA, E + 1))
+    if gh_in is not None:
+        _f32c("noisy_head_bwd: gh_in", gh_in, (B, T, A, E))
+    a = _lib.NoisyBwdArgs(gchosen=_p(gchosen), actions=_p(actions), act_sb=actions.stride(0), act_st=actions.stride(1),
+                          h=_p(h), u_w=_p(u_w), s_w=_p(s_w), eps_w=_p(eps_w), gh_in=_p(gh_in), gh_out=_p(gh_out),
+                          gpart=_p(gpart), h_ts=h.shape[1], B=B, T=T, A=A, E=E, NA=NA)
+    fn = lib().t2o_noisy_head_bwd
+
+    def go(t_lo, t_hi):
+        a.t_lo, a.t_hi = int(t_lo), int(t_hi)
+        _mark(timer, "begin:noisy_bwd")
+        check(fn(ctypes.byref(a), stream_ptr(h.device)), "noisy_head_bwd")
+        _mark(timer, "end:noisy_bwd")
+    if launcher:
+        return go, gh_out, gpart
+    go(*(steps if steps is not None else (0, T)))
+    return gh_out, gpart
+
+
+def noisy_head_wgrad(gpart, B, A, du_w, du_b, ds_w=None, ds_b=None, eps=None, timer=None):
+    """du_w, du_b += Σ_t gpart[t];  ds_w, ds_b += Σ_t eps[t] ⊙ gpart[t]  (fixed order;
+    the slots are views of the caller's flat gradient).  eps None: the mean head."""
+    T, P, NA, E1 = gpart.shape
+    E = E1 - 1
+    _f32c("noisy_head_wgrad: gpart", gpart, (T, noisy_head_parts(B, A), NA, E1))
+    _f32c("noisy_head_wgrad: du_w", du_w)
+    _f32c("noisy_head_wgrad: du_b", du_b)
+    assert du_w.numel() == NA * E and du_b.numel() == NA
+    eps_w = eps_b = None
+    if eps is not None:
+        eps_w, eps_b = eps
+        _f32c("noisy_head_wgrad: eps_w", eps_w, (eps_w.shape[0], NA, E))
+        _f32c("noisy_head_wgrad: eps_b", eps_b, (eps_w.shape[0], NA))
+        _f32c("noisy_head_wgrad: ds_w", ds_w)
+        _f32c("noisy_head_wgrad: ds_b", ds_b)
+        assert eps_w.shape[0] >= T and ds_w.numel() == NA * E and ds_b.numel() == NA
+    a = _lib.NoisyWgradArgs(gpart=_p(gpart), eps_w=_p(eps_w), eps_b=_p(eps_b), du_w=_p(du_w), du_b=_p(du_b),
+                            ds_w=_p(ds_w), ds_b=_p(ds_b), B=int(B), T=T, A=int(A), E=E, NA=NA)
+    _mark(timer, "begin:noisy_wgrad")
+    check(lib().t2o_noisy_head_wgrad(ctypes.byref(a), stream_ptr(gpart.device)), "noisy_head_wgrad")
+    _mark(timer, "end:noisy_wgrad")
+
+
 def select_actions(q, avail, epsilon=0.0, seed=0, counter=0, out=None):
     """ε-greedy actions (include/t2omca.h t2o_select_actions): q f32 [..., NA] and
     avail i32 [..., NA], dense; returns int64 [...] (or writes `out`)."""

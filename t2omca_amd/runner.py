@@ -26,6 +26,13 @@ the env kernel; the batch dict holds the [n, T+1, ...] views the learner takes
 ε schedule: PyMARL's DecayThenFlatSchedule (linear), evaluated per rollout at
 t_env as the reference's selector does; test_mode selects greedily.
 
+A NoisyNet agent (modules.TransformerAgent with action_selector "noisy-new",
+``agent.noisy``): a non-test run draws the episode's noise once
+(t2o_noise_normal: kind "runner", this runner's seed, counter = ``episode``) and
+applies the noisy head to each step's h before select_actions (one more launch per
+step, t2o_noisy_head_fwd); the ε schedule still applies as configured.  test_mode
+runs the mean head, which is the fused step: no new launch.
+
 compact_obs=True (the env must be a VecEnv(wire=True)): the
 batch carries the observation wire format instead of the dense obs —
 ``obs_wire`` [n, T+1, A, 4] int32 plus the per-episode normaliser snapshot
@@ -105,6 +112,10 @@ class RolloutRunner:
         if env.A != agent.shape.n_ent or env.n_actions != agent.shape.NA:
             raise ValueError("agent and env disagree on agents / actions")
         self.agent, self.env = agent, env
+        # a NoisyNet head (modules.TransformerAgent, action_selector "noisy-new"): non-test
+        # runs explore through it (noise kind "runner", seed = this runner's, counter =
+        # episode), under the ε schedule as configured; test runs use the mean head
+        self.noisy = bool(getattr(agent, "noisy", False))
         self.precision = precision
         self.shape = dataclasses.replace(agent.shape, prec=1) if precision == "bf16" else agent.shape
         self.n, self.T, self.A, self.NA = env.n_envs, env.T, env.A, env.n_actions
@@ -159,8 +170,16 @@ class RolloutRunner:
             self._bufs = self._alloc()
         tm = self._bufs
         env, shape = self.env, self.shape
-        pack = ops.pack_params(shape, torch.cat([p.detach().reshape(-1) for p in self.agent.parameters()]))
+        flat = torch.cat([p.detach().reshape(-1) for p in self.agent.parameters()])
+        pack = ops.pack_params(shape, flat[:shape.n_params])  # (a noisy agent's sigmas follow the plain prefix)
         eps = 0.0 if test_mode else self.schedule.eval(self.t_env)
+        noise = head = None
+        if self.noisy and not test_mode:
+            # the episode's ε, once: step t's slice serves that step's one forward call
+            nl = self.agent.q_basic
+            head = [p.detach().contiguous() for p in (nl.u_w, nl.u_b, nl.s_w, nl.s_b)]
+            noise = ops.noise_normal(shape.E, shape.NA, self.T + 1, self.seed, "runner", self.episode,
+                                     device=self.device)
         env.reset(dest=self._dest(tm, 0))
         ret = torch.zeros(self.n, dtype=torch.float64, device=self.device)
         h = None
@@ -170,6 +189,8 @@ class RolloutRunner:
             obs_t = self._obs_step if self.compact_obs else tm["obs"][t]
             q, h_seq = ops.agent_unroll_fwd(shape, pack, obs_t.unsqueeze(1), h0_on=h, timer=timer)
             h = h_seq.view(self.n * self.A, shape.E)
+            if noise is not None:  # the noisy head's q over the fused step's mean-head q
+                ops.noisy_head_fwd(h_seq, q, *head, eps=(noise[0][t:t + 1], noise[1][t:t + 1]), timer=timer)
             counter = (self.episode * (self.T + 1) + t)
             mark("begin:select_actions")
             ops.select_actions(q[:, 0], tm["avail_actions"][t], eps, self.seed, counter,
@@ -276,7 +297,7 @@ class RolloutRunner:
     def _built_with(self):
         s = self.schedule
         return {"epsilon_schedule": [s.start, s.finish, s.time_length], "precision": self.precision,
-                "compact_obs": self.compact_obs}
+                "compact_obs": self.compact_obs, "noisy": self.noisy}
 
     def state_dict(self):
         """t_env, the episode count (the ε-greedy draw counter), the seed in use, the
@@ -287,6 +308,7 @@ class RolloutRunner:
                 "acc": None if self._acc is None else self._acc.detach().cpu(), "n_acc": list(self._n_acc)}
 
     def load_state_dict(self, sd):
+        sd = {"noisy": False, **sd}  # (a state saved before the noisy head existed: a plain agent)
         check_fields("RolloutRunner", sd, {"format": 1, **self._built_with()})
         if (sd["acc"] is None) != (self._acc is None):
             raise ValueError(f"RolloutRunner state: acc (the statistics accumulators) is "
