@@ -18,7 +18,8 @@ Oracle: oracle/ref_learner.td_forward in fp64 (pinned to the reference modules'
 goldens by tests/test_oracle_golden.py; TD semantics parity-unpinned).
 Bars (normwise max|Δ| / max|ref|):
   fp32   Q_tot, targets, priorities <= 1e-5; parameter gradients <= 3e-5 against the
-         tie-aware oracle (below);
+         tie-aware oracle (below), flat and in every parameter block on the block's own
+         maximum (tests/grad_blocks.py);
   bf16   Q_tot, targets, priorities <= 2e-2; gradients <= 6e-2; agent Q at every
          t <= 4e-2 (bf16 MFMA operands, fp32 accumulation / LayerNorm / softmax /
          recurrent state).  Measured on the box (profiles/r3_a/pytest.log), bf16:
@@ -52,6 +53,7 @@ import torch
 
 from oracle import ref_learner, ref_model
 from tests.gpu_util import normwise, oracle_td_tie_aware, require_gpu
+from tests.grad_blocks import assert_blocks_fp32
 
 pytestmark = pytest.mark.gpu
 
@@ -119,6 +121,7 @@ def _td_vs_oracle(A, B, T, precision, seed=3):
         _, _, ref_t, ties = oracle_td_tie_aware(pa, pm, _cfg(A), batch, w, g, margin=RELU_MARGIN)
         errs["grad_tie_aware"] = normwise(g, ref_t)
         print(f"A={A} B={B} T={T} relu ties", ties)
+        errs["blocks"] = (g, ref_t, pa, pm, f"configs ({A},{B},{T})")
     return errs, learner, batch, ex
 
 
@@ -139,10 +142,14 @@ def _agent_q_per_t(learner, batch, ex, precision, label):
 
 def _check(errs, precision):
     tol = TOL[precision]
+    blocks = errs.pop("blocks", None)
     print(precision, {k: f"{v:.2e}" for k, v in errs.items()})
     assert errs["qtot"] < tol["q"] and errs["targets"] < tol["q"] and errs["prio"] < tol["q"], errs
     # fp32: against the tie-aware oracle (_td_vs_oracle); bf16: plain
     assert errs.get("grad_tie_aware", errs["grad"]) < tol["g"], errs
+    if blocks is not None:  # fp32: every parameter block < 3e-5 of its own maximum (tests/grad_blocks.py)
+        g, ref_t, pa, pm, tag = blocks
+        assert_blocks_fp32(g, ref_t, pa, pm, tag=tag)
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])

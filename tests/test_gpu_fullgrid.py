@@ -16,7 +16,8 @@ batch (per_run.py:224-238 is the caller: one learner.train per replay batch):
     operands of an episode are the same in both runs), and the Σ mask slots add up
     exactly;
   * one slice of the same batch matches the fp64 oracle (the fp32 bar 1e-5 / 3e-5
-    tie-aware, bf16 2e-2 / 6e-2 as test_gpu_configs.py).
+    tie-aware, the gradient also per parameter block; bf16 2e-2 / 6e-2 as
+    test_gpu_configs.py).
 
 Masks are ragged (episodes end early: terminated at their last step, filled 0
 after), as a PyMARL replay batch is.  The slices run the same kernel families as the
@@ -29,6 +30,7 @@ import pytest
 import torch
 
 from tests.gpu_util import normwise, oracle_td_tie_aware, require_gpu
+from tests.grad_blocks import assert_blocks_fp32
 
 pytestmark = pytest.mark.gpu
 
@@ -136,6 +138,8 @@ def _run(A, B, T, precision, S, n_oracle):
     tol = TOL[precision]
     assert errs["qtot"] < tol["q"] and errs["targets"] < tol["q"] and errs["prio"] < tol["q"], errs
     assert errs["grad"] < tol["g"], errs
+    if precision == "fp32":  # and every parameter block on its own scale (tests/grad_blocks.py)
+        assert_blocks_fp32(g, ref_g, pa, pm, tag=f"full grid A={A} slice of {n_oracle}")
 
 
 @pytest.mark.parametrize("precision", ["bf16", "fp32"])

@@ -7,6 +7,7 @@ import torch
 
 from oracle import ref_learner, ref_model
 from tests.gpu_util import flat_from_npz, normwise, require_gpu, tuned_fixtures
+from tests.grad_blocks import assert_blocks_fp32, module_seed
 from tests.test_oracle_golden import _cfg
 
 pytestmark = pytest.mark.gpu
@@ -18,10 +19,12 @@ def _cfg_dict(A):
                 n_actions=5, state_entity_feats=8, mixer_emb=32, mixer_heads=3, mixer_depth=2)
 
 
-def _setup(A, seed=0):
+def _setup(A, seed=None):
+    """The modules of a whole-update case, drawn with grad_blocks.module_seed(A) (which
+    leaves every parameter block a gradient to compare)."""
     from t2omca_amd.modules import TransformerAgent, TransformerMixer
     from t2omca_amd.synthetic import make_args
-    torch.manual_seed(seed)
+    torch.manual_seed(module_seed(A) if seed is None else seed)
     args = make_args(A)
     agent = TransformerAgent(None, args).cuda()
     mixer = TransformerMixer(args).cuda()
@@ -37,12 +40,13 @@ def test_td_update_matches_oracle(A, B, T, lam):
     from t2omca_amd.synthetic import make_batch
     agent, mixer, pa, pm = _setup(A)
     learner = TDLearner(agent, mixer, td_lambda=lam)
-    batch, w = make_batch(B, T, A, seed=3)
+    cpu, w = make_batch(B, T, A, seed=3, device="cpu")  # (fitness per block: computed without a device)
+    batch, w = {k: v.cuda() for k, v in cpu.items()}, w.cuda()
     # make the target networks differ from the online ones
-    learner.target_params.add_(0.01 * torch.randn_like(learner.target_params))
+    gen = torch.Generator().manual_seed(1)
+    learner.target_params.add_((0.01 * torch.randn(learner.target_params.numel(), generator=gen)).cuda())
     learner._pack_targets()
     cfg = _cfg_dict(A)
-    cpu = {k: v.cpu() for k, v in batch.items()}
     cpu_d = {k: (v.double() if v.is_floating_point() else v) for k, v in cpu.items()}
     tgt = learner.target_params.cpu().double()
     pat, pmt, off = {}, {}, 0
@@ -65,6 +69,7 @@ def test_td_update_matches_oracle(A, B, T, lam):
     g = (learner.grad[:-1] / learner.grad[-1]).cpu()
     ref_g = torch.cat([v.grad.reshape(-1) for v in list(pa_g.values()) + list(pm_g.values())])
     assert normwise(g, ref_g) < 3e-5
+    assert_blocks_fp32(g, ref_g, pa, pm, tag=f"learner ({A},{B},{T}) lam {lam}")  # each block on its own scale
     # the parameter update equals clip_grad_norm_(10) + Adam applied to those grads
     p0 = torch.cat([v.reshape(-1) for v in list(pa.values()) + list(pm.values())]).float()
     ref_p = p0.clone().requires_grad_(True)

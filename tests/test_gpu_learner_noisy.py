@@ -5,7 +5,7 @@ ref_learner.td_forward up when called, so the noisy version, bound to the update
 is substituted with monkeypatch.setattr).
 
 Inputs are those of tests/test_gpu_learner_masks.py (its helpers imported): modules
-torch.manual_seed(0), batch seed 3 drawn on the CPU, masked_avail seed 103, target
+torch.manual_seed(grad_blocks.module_seed(A)) (0; 4 at 16 AGVs), batch seed 3 drawn on the CPU, masked_avail seed 103, target
 parameters (sigmas included) perturbed by 0.01·N(0, 1); the sigmas are 0.3·N(0, 1)
 from a generator seeded 7, the learner's noise_seed is 11.  The oracle takes the ε the
 learner drew (learner.last_noise), which is first held to one fp32 ulp of the numpy
@@ -20,7 +20,7 @@ the masked argmax under the noisy online Q differs from the mean-head one at >= 
 
   case                   moved   gap        targets vs ε=0   argmax differs
   (8, 6, 5) exact        0.490   5.13e-04   1.97e+00         0.438
-  (16, 3, 4) pipelined   0.537   2.74e-03   1.35e+00         0.450
+  (16, 3, 4) pipelined   0.412   1.21e-03   1.42e+00         0.517
   (5, 4, 6) runtime      0.571   9.30e-03   7.79e+00         0.371
   (8, 3, 5) E64/H4       0.438   3.16e-03   9.75e-01         0.486
   (8, 6, 5) Q(λ)         0.490   5.13e-04   1.79e+00         0.438
@@ -54,6 +54,7 @@ import torch.multiprocessing as mp
 
 from tests import noisy_model as nm
 from tests.gpu_util import normwise, require_gpu, split_flat
+from tests.grad_blocks import module_seed
 from tests.test_gpu_generic import _args, _cfg_of
 from tests.test_gpu_learner_masks import (SEED, TOL, Snapshot, check_update, masked_batch, perturb_targets, to_cuda,
                                           update)
@@ -70,10 +71,11 @@ def _kernel_family(monkeypatch):
     monkeypatch.delenv("T2O_MIXER_SPLIT", raising=False)
 
 
-def noisy_modules(cfg, device="cuda", seed=0):
-    """The noisy agent and the mixer of a config (module seed 0), sigmas 0.3·N(0, 1)."""
+def noisy_modules(cfg, device="cuda", seed=None):
+    """The noisy agent and the mixer of a config (module seed grad_blocks.module_seed(A)
+    unless given), sigmas 0.3·N(0, 1)."""
     from t2omca_amd.modules import TransformerAgent, TransformerMixer
-    torch.manual_seed(seed)
+    torch.manual_seed(module_seed(cfg["n_agents"]) if seed is None else seed)
     args = _args(cfg, device=device)
     args.action_selector = "noisy-new"
     agent, mixer = TransformerAgent(None, args), TransformerMixer(args)

@@ -14,7 +14,7 @@ argmax ones): the share of (b, t) with |Q'_t − Qk_t| > 1e-3·max|Q'| is >= 0.5
 Q(λ) targets differ from the TD(λ) targets of the same target mix by >= 1e-2 normwise
 — a learner that dropped the correction, or fed the kernel the double-Q mix twice,
 fails the targets bar by orders of magnitude.  Computed on the CPU at seed 3:
-share 1.000 at (8,6,5), (3,5,4), (16,3,4) and (5,4,6); difference 2.1 - 3.1.
+share 1.000 at (8,6,5), (3,5,4), (16,3,4) and (5,4,6); difference 1.1 - 3.1.
 
 The RMSprop transition is checked, like the Adam one in test_gpu_learner_steps.py, on
 the learner's own normalised gradient against rmsprop_ref.  bf16 operands do not reach

@@ -113,12 +113,12 @@ def test_updates_follow_oracle_and_adam(A, T, piped, variant):
     kw = dict(target_update_interval=INTERVAL)
     if variant == "clip":
         # half the oracle's gradient norm at update 0, so the clip engages there
-        _, pa, pm = make_learner(cfg)
+        _, pa, pm = make_learner(cfg, model_seed=0)
         ref_g = oracle_td_tie_aware(pa, pm, cfg, batches[0][0], batches[0][1])[2]
         kw["grad_norm_clip"] = 0.5 * float(ref_g.norm())
     else:
         kw["weight_decay"] = 1e-2
-    learner, pa, pm = make_learner(cfg, **kw)
+    learner, pa, pm = make_learner(cfg, model_seed=0, **kw)
     first_step = 1
     if variant == "weight_decay":  # (module docstring: no checked step from zero moments)
         cpu, w = masked_batch(A, max(SIZES), T, 2)
@@ -136,7 +136,9 @@ def test_updates_follow_oracle_and_adam(A, T, piped, variant):
         pa_s, pm_s = split_flat(snap.params, pa, pm)
         pa_t, pm_t = split_flat(snap.targets, pa, pm)
         errs, _, _ = check_update(f"A={A} {variant} update {u}", learner, pa_s, pm_s, cfg, cpu, w, out,
-                                  pa_tgt=pa_t, pm_tgt=pm_t)
+                                  pa_tgt=pa_t, pm_tgt=pm_t, blocks=False)  # (flat only: the ragged batches'
+        # fitness for a per-block comparison is not established; the first update's shapes have it in
+        # test_gpu_learner_masks.py)
         # (ii) the Adam transition on the learner's own gradient
         graw = out[0]
         ref = adam_ref(snap.params, graw[:-1], snap.m, snap.v, snap.step + 1, lr=learner.lr, betas=learner.betas,
