@@ -145,10 +145,7 @@ int launch_mixer_fwd(const MixerFwdArgs& args, int nnet, hipStream_t stream) {
   auto kern = wide ? (a.wlds ? mixer_fwd_kernel<E, H, D, A, FF, RT, true, WT, Dm::QT == 1 ? 512 : 256>
                              : mixer_fwd_kernel<E, H, D, A, FF, RT, false, WT, Dm::QT == 1 ? 512 : 256>)
                    : (a.wlds ? mixer_fwd_kernel<E, H, D, A, FF, RT, true, WT> : mixer_fwd_kernel<E, H, D, A, FF, RT, false, WT>);
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  dim3 grid((args.B + a.waves - 1) / a.waves, nnet);
-  hipLaunchKernelGGL(kern, grid, dim3(64 * a.waves), lds, stream, a);
-  return (int)hipGetLastError();
+  return mix_launch(kern, dim3((args.B + a.waves - 1) / a.waves, nnet), 64 * a.waves, lds, stream, a);
 }
 
 // ---------------------------------------------------------------------------
@@ -180,9 +177,8 @@ __global__ __launch_bounds__(256) void mixer_bwd_kernel(MixerBwdArgs args) {
   const int w = wave_id();
   float* X0 = smem + args.lds_w + w * Bd::PERW;
   float* X0T = X0 + Dm::X0F;  // (KM 1: the transposed key block)
-  float* WORK = X0T + Bd::X0TF;
-  float* GOUTB = Bd::GOUT ? WORK : WORK;        // head grads (rows of OUT layout)
-  float* stage = WORK + Bd::GOUT;               // staging / gX0 region
+  float* GOUT = X0T + Bd::X0TF;   // head grads, rows of OUT layout: a region of their own with
+  float* stage = GOUT + Bd::GOUT;  // several query tiles, else aliasing the staging / gX0 region
   float* gs = args.slabs + (size_t)blockIdx.x * G.grad_total;
   // the forward section of the pack in LDS when it fits
   // beside the per-wave buffers, else read through L2 (large mixers)
@@ -198,13 +194,7 @@ __global__ __launch_bounds__(256) void mixer_bwd_kernel(MixerBwdArgs args) {
   // order, read by the contraction as 16-record tiles (t2o_bwd_tape_tiles); the
   // last tile's records past the stream's end are zeros
   const size_t nrec = (size_t)fa.B * n.T * nq, ctiles = (nrec + 15) / 16;
-  if (blockIdx.x == 0 && w == 0) {
-    const int tail = (int)(ctiles * 16 - nrec) * Rec::SIZE;  // elements
-    for (int d = 0; d < D; ++d) {
-      WT* z = static_cast<WT*>(args.tape) + ((size_t)d * ctiles * 16 + nrec) * Rec::SIZE;
-      for (int i = lane_c() + 16 * lane_g(); i < tail; i += 64) z[i] = WT(0.f);
-    }
-  }
+  if (blockIdx.x == 0 && w == 0) tape_zero_tail<D, Rec, WT>(args.tape, nrec);
   const int f = lane < E ? lane : 0;
   const bool fv = lane < E;
   // state embedding grads as MFMA tiles: lane (g, c) reg r = dWe[16ft+4g+r][c]
@@ -252,7 +242,6 @@ __global__ __launch_bounds__(256) void mixer_bwd_kernel(MixerBwdArgs args) {
       // ---- mixing head backward (lanes = features)
 #pragma unroll
       for (int k = 0; k < 3; ++k) ghw[k] += cur.ghx[k];
-      float* GOUT = Bd::GOUT ? GOUTB : stage;
       mixer_head_bwd<E, A, WT, Bd::LDB>(P, L, OUT, GOUT, cur.m.qs[0], cur.gy, ghw, args.gqv + bt * na + lane, gWo, gbo, na,
                            RT ? L.pos_func : T2O_POS_ABS, RT ? L.pos_beta : 1.f);
       for (int i = nq * Bd::LDB + lane; i < Bd::OUTB; i += 64) GOUT[i] = 0.f;
@@ -434,26 +423,16 @@ __global__ __launch_bounds__(256) void mixer_bwd_kernel(MixerBwdArgs args) {
 // dW staging, then the hand-over 1 -> 0 [block-1 key grads (rows < LK) | grad
 // wrt the block-1 input (query rows, in R's padding rows)], then the step's
 // total key grads written by the block-0 wave, whose hyper rows the block-1
-// wave reads at its next backward.  Per-step math, records and slab sums are
-// those of mixer_bwd_kernel; the block cache is the lean one (MixerCacheLean)
-// so that a wave fits half a register file (two waves per SIMD), and records
-// are written through MaskedRec (tape tiles of exactly the Q query rows).
+// wave reads at its next backward (t2o_mixer_parts.hpp PairDims).  Per-step math,
+// records and slab sums are those of mixer_bwd_kernel; the block cache is the
+// lean one (MixerCacheLean) so that a wave fits half a register file (two waves
+// per SIMD), and records are written through MaskedRec (tape tiles of exactly
+// the Q query rows).
+// (pair region: head rows / dW staging, all A + 3 query rows handed over)
 template <int E, int A>
-struct MixPipeDims {
-  using Dm = MixDims<E, A>;
-  using Bd = MixBwdDims<E, A>;
-// Row stride of the pair region's [row][feature] blocks.  E + 4 (the other
-// kernels' LDO) removes their T-layout bank conflicts here too, but measured slower
-// in this register-bound kernel: interleaved A/B, overlapped, 3 rounds
-// (profiles/r3_ab2/): mixer_bwd 0.618 ms at E vs 0.630 at E + 4.
-  static constexpr int LDR = E;
-  static constexpr int XCH = Dm::LKCAP * LDR;  // offset of the query-row grads in R
-  static constexpr int R0 = Bd::W0 > Dm::KT * 16 * LDR ? Bd::W0 : Dm::KT * 16 * LDR;
-  // (the hand-over needs R to hold the key grads and, past them, the query-row grads)
-  static constexpr int REGION = R0 > XCH + Dm::QCAP * LDR ? R0 : XCH + Dm::QCAP * LDR;
-  static constexpr int PAIRF = Dm::X0F + REGION;
-  static constexpr bool OK = Dm::QT == 1;
-};
+using MixPipeDims = PairDims<E, A, MixBwdDims<E, A>::W0, MixDims<E, A>::QCAP>;
+template <int E, int A>
+constexpr bool mixp_ok = MixDims<E, A>::QT == 1;  // one query tile
 
 // T2O_MIXER_BWD=single selects the one-wave kernel (A/B timing, parity cross-check)
 inline bool mixer_bwd_single_wave() {
@@ -529,22 +508,6 @@ T2O_DEV void mixp_load(const MixerBwdArgs& args, int b, int t, MixPIn<E, A>& in,
     in.xm[ft] = c < nq ? ld4(args.xmid + (bt * nq + c) * E + 16 * ft + 4 * g) : zero4();
 }
 
-template <int E, int A>
-T2O_DEV void mixp_load_stT(const MixerFwdArgs& fa, int b, int t, f4 (&stT)[MixDims<E, A>::ST], int na) {
-  using Dm = MixDims<E, A>;
-  const int c = lane_c(), g = lane_g();
-  const float* st = fa.states + b * fa.st_sb + t * fa.st_st;
-#pragma unroll
-  for (int s = 0; s < Dm::ST; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 16 * s + 4 * g + r;
-      float v = ld_or0(st, j * fa.Fs + c, j < na && c < fa.Fs);
-      if (j < na && c == fa.Fs) v = 1.f;
-      stT[s][r] = v;
-    }
-}
-
 // block-1 wave: key block + block-1 recompute, then head + block-1 backward
 template <int E, int H, int A, int FF, typename WT>
 T2O_DEV void mixp_block1(const MixerBwdArgs& args, const Wts<WT>& P0, const t2o_layout& L, const t2o_layout& G,
@@ -564,7 +527,7 @@ T2O_DEV void mixp_block1(const MixerBwdArgs& args, const Wts<WT>& P0, const t2o_
   const int c = lane_c(), g = lane_g(), lane = threadIdx.x & 63;
   const int f = lane < E ? lane : 0;
   const bool fv = lane < E;
-  // block 1's compact record stream (mixer_bwd_kernel)
+  // block 1's compact record stream (t2o_mixer_block.hpp tape_zero_tail)
   const size_t ctiles = ((size_t)fa.B * T * nq + 15) / 16;
   constexpr size_t RECD = 1;  // tape block
   f4 ln2[2 * ET];
@@ -683,7 +646,7 @@ T2O_DEV void mixp_block0(const MixerBwdArgs& args, const Wts<WT>& P0, const t2o_
     MixerCacheLean<E, H, KT, FF> cache;
     KeyFrags<E, KT, BF> K;
     {  // ---- recompute: block-0 forward with cache (queries = X0's last na+3 rows)
-      mixp_load_stT<E, A>(fa, b, t, stT, na);  // for this step's state-embedding grads
+      mix_load_stT<E, A>(fa, b, t, stT, na);  // for this step's state-embedding grads
       const Wts<WT> P = step_view(P0);
       K.template load<Dm::LDX>(X0);
       f4 x[ET];
@@ -760,7 +723,6 @@ T2O_DEV void mixp_block0(const MixerBwdArgs& args, const Wts<WT>& P0, const t2o_
     vec_accumulate_g<ET>(gs + Gb.g2[0], &ln2[0]);
     vec_accumulate_g<ET>(gs + Gb.n2[0], &ln2[ET]);
   });
-  (void)fv;
 }
 
 template <typename WT>
@@ -770,7 +732,7 @@ inline __host__ __device__ int64_t mixp_weight_elems(const t2o_layout& L) {
 
 template <int E, int H, int D, int A, int FF, int RT, typename WT>
 T2O_DEV void mixer_bwd_pipe_body(const MixerBwdArgs& args, const t2o_layout& L, const t2o_layout& G) {
-  static_assert(D == 2 && MixPipeDims<E, A>::OK, "one wave per block of a depth-2 stack, one query tile");
+  static_assert(D == 2 && mixp_ok<E, A>, "one wave per block of a depth-2 stack, one query tile");
   using Dm = MixDims<E, A>;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   T2O_LDS_POISON(smem);
@@ -796,15 +758,8 @@ T2O_DEV void mixer_bwd_pipe_body(const MixerBwdArgs& args, const t2o_layout& L, 
     for (int i = threadIdx.x & 63; i < Dm::X0F; i += 64) X0[i] = 0.f;
   int* const flags = reinterpret_cast<int*>(smem + args.lds_w + args.waves * MixPipeDims<E, A>::PAIRF);
   if (threadIdx.x < PAIR_FLAG_FLOATS) flags[threadIdx.x] = 0;
-  if (blockIdx.x == 0 && threadIdx.x < 64) {  // zero each block's compact stream past its last record
-    using Rec = TapeRec<E, H, FF>;
-    const size_t nrec = (size_t)args.f.B * args.f.net[0].T * (na + 3), ctiles = (nrec + 15) / 16;
-    const int tail = (int)(ctiles * 16 - nrec) * Rec::SIZE;
-    for (int dd = 0; dd < D; ++dd) {
-      WT* z = static_cast<WT*>(args.tape) + ((size_t)dd * ctiles * 16 + nrec) * Rec::SIZE;
-      for (int i = threadIdx.x; i < tail; i += 64) z[i] = WT(0.f);
-    }
-  }
+  if (blockIdx.x == 0 && threadIdx.x < 64)
+    tape_zero_tail<D, TapeRec<E, H, FF>, WT>(args.tape, (size_t)args.f.B * args.f.net[0].T * (na + 3));
   __syncthreads();
   PairBarrier pb = PairBarrier::make(flags, w);  // partner: the pair's other wave
   const int b = blockIdx.x * args.waves + pr;  // the launcher makes every pair valid
@@ -842,7 +797,7 @@ int launch_mixer_bwd(MixerBwdArgs& args, int max_slabs, int* nslab, hipStream_t 
   constexpr int PERW = MixBwdDims<E, A, key_mode<MixDims<E, A>::KT, WT>()>::PERW;
   const t2o_layout& L = args.f.L;
   args.lds_w = (int)((lds_weight_floats<WT>(L, L.fwd_total) + 15) / 16 * 16);
-  if constexpr (D == 2 && MixPipeDims<E, A>::OK) {
+  if constexpr (D == 2 && mixp_ok<E, A>) {
     if (args.xmid && !mixer_bwd_single_wave()) {
       const int lds_w = (int)((lds_weight_floats<WT>(L, mixp_weight_elems<WT>(L)) + 15) / 16 * 16);
       for (int pairs = 4; pairs >= 1; pairs >>= 1) {
@@ -853,11 +808,8 @@ int launch_mixer_bwd(MixerBwdArgs& args, int max_slabs, int* nslab, hipStream_t 
         args.lds_w = lds_w;
         const int grid = args.f.B / pairs;
         if (grid > max_slabs) return T2O_EINVAL;
-        auto kern = mixer_bwd_pipe_kernel<E, H, D, A, FF, RT, WT>;
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(128 * pairs), lds, stream, args);
         *nslab = grid;
-        return (int)hipGetLastError();
+        return mix_launch(mixer_bwd_pipe_kernel<E, H, D, A, FF, RT, WT>, dim3(grid), 128 * pairs, lds, stream, args);
       }
     }
   }
@@ -871,10 +823,8 @@ int launch_mixer_bwd(MixerBwdArgs& args, int max_slabs, int* nslab, hipStream_t 
   const int grid = (args.f.B + args.waves - 1) / args.waves;
   if (grid > max_slabs) return T2O_EINVAL;
   auto kern = wlds ? mixer_bwd_kernel<E, H, D, A, FF, RT, true, WT> : mixer_bwd_kernel<E, H, D, A, FF, RT, false, WT>;
-  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * args.waves), lds, stream, args);
   *nslab = grid;
-  return (int)hipGetLastError();
+  return mix_launch(kern, dim3(grid), 64 * args.waves, lds, stream, args);
 }
 
 }  // namespace

@@ -430,4 +430,18 @@ T2O_DEV void mixer_block_bwd_lean(const Wts<WT>& P, const t2o_layout& L, float* 
   for (int t = 0; t < ET; ++t) gx[t] = gxp[t] + gres[t];
 }
 
+// Each block's records form one compact tape stream of nrec records, (step,
+// episode, query row) in order, read by the contraction as 16-record tiles
+// (t2o_bwd_tape_tiles): zero the last tile's records past the stream's end.
+// Called by one wave of the launch.
+template <int D, typename Rec, typename WT>
+T2O_DEV void tape_zero_tail(void* tape, size_t nrec) {
+  const size_t ctiles = (nrec + 15) / 16;
+  const int tail = (int)(ctiles * 16 - nrec) * Rec::SIZE;  // elements
+  for (int d = 0; d < D; ++d) {
+    WT* z = static_cast<WT*>(tape) + ((size_t)d * ctiles * 16 + nrec) * Rec::SIZE;
+    for (int i = threadIdx.x & 63; i < tail; i += 64) z[i] = WT(0.f);
+  }
+}
+
 }  // namespace t2o

@@ -1,8 +1,14 @@
 // t2o_mixer_parts.hpp — what the mixer kernels share (t2o_mixer.hip: one wave
 // per episode; t2o_mixer_split.hip: the multi-tile mixers decoupled into the
 // hyper-token recurrence and the per-(episode, step) agent rows): argument
-// blocks, compile-time dims, the per-step input loads, the key block, and the
-// mixing head forward / backward.  Reference: n_transf_mixer.py:55-103.
+// blocks, compile-time dims, the per-step input loads, the key block, the
+// mixing head forward / backward, the pair kernels' LDS region and the launch
+// helper.  Reference: n_transf_mixer.py:55-103.
+// Not here: the other per-step fragments the five BPTT bodies repeat (hyper rows
+// into X0, state-embedding grads and their flush, key grads to LDS rows, the hwp /
+// ghw_ext loads).  As forced-inline helpers they changed no arithmetic but moved
+// the register allocation of those register-bound kernels, spills and time with
+// it; tables and timings in profiles/mixer_step_helpers/ (README.txt).
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -286,6 +292,23 @@ struct MixBwdIn {
   f4 stT[Dm::ST];  // lane (g, c) reg r: state feature c of entity 16s + 4g + r; column Fs = 1 (bias)
 };
 
+// The state tile of step t transposed, the B operand of the state-embedding grads:
+// lane (g, c) reg r = state feature c of entity 16s + 4g + r; column Fs = 1 (bias)
+template <int E, int A>
+T2O_DEV void mix_load_stT(const MixerFwdArgs& fa, int b, int t, f4 (&stT)[MixDims<E, A>::ST], int na) {
+  const int c = lane_c(), g = lane_g();
+  const float* st = fa.states + b * fa.st_sb + t * fa.st_st;
+#pragma unroll
+  for (int s = 0; s < MixDims<E, A>::ST; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = 16 * s + 4 * g + r;
+      float v = ld_or0(st, j * fa.Fs + c, j < na && c < fa.Fs);
+      if (j < na && c == fa.Fs) v = 1.f;
+      stT[s][r] = v;
+    }
+}
+
 template <int E, int A, int D, bool XM = true>
 T2O_DEV void mixb_load(const MixerBwdArgs& args, const MixerNet& n, int b, int t, MixBwdIn<E, A, D>& in, int na) {
   using Dm = MixDims<E, A>;
@@ -322,6 +345,8 @@ T2O_DEV void mixb_load(const MixerBwdArgs& args, const MixerNet& n, int b, int t
               q < nq ? ld4(args.xmid + ((bt * (D - 1) + d - 1) * nq + q) * E + 16 * ft + 4 * g) : zero4();
     }
   }
+  // (mix_load_stT's loop, written out: through the helper four mixer_bwd_kernel instances
+  // spilled up to 22 registers more, profiles/mixer_step_helpers/regs_t2o_mixer_stT_in_mixb_load.txt)
   const float* st = fa.states + b * fa.st_sb + t * fa.st_st;
 #pragma unroll
   for (int s = 0; s < Dm::ST; ++s)
@@ -357,6 +382,25 @@ struct MixBwdDims {
   static constexpr int W0 = OUTB > STAGE ? OUTB : STAGE;
   static constexpr int WORK = GOUT + (W0 > GX0B ? W0 : GX0B);
   static constexpr int PERW = Dm::X0F + X0TF + WORK;
+};
+
+// LDS of a two-wave (one per block) BPTT pair: the key block X0 and one region R
+// owned by whichever wave is in its backward phase — STAGEF floats of head rows /
+// dW staging, then the hand-over 1 -> 0 [block-1 key grads (rows < lk) | the grads
+// wrt the block-1 input, QROWS query rows], then the step's total key grads.
+template <int E, int A, int STAGEF, int QROWS>
+struct PairDims {
+  using Dm = MixDims<E, A>;
+  // Row stride of the region's [row][feature] blocks.  E + 4 (the other kernels'
+  // LDO) removes their T-layout bank conflicts here too, but measured slower in the
+  // register-bound one-tile pair kernel: interleaved A/B, overlapped, 3 rounds
+  // (profiles/r3_ab2/): mixer_bwd 0.618 ms at E vs 0.630 at E + 4.
+  static constexpr int LDR = E;
+  static constexpr int XCH = Dm::LKCAP * LDR;  // offset of the query-row grads in R
+  static constexpr int R0 = STAGEF > Dm::KT * 16 * LDR ? STAGEF : Dm::KT * 16 * LDR;
+  // (the hand-over needs R to hold the key grads and, past them, the query-row grads)
+  static constexpr int REGION = R0 > XCH + QROWS * LDR ? R0 : XCH + QROWS * LDR;
+  static constexpr int PAIRF = Dm::X0F + REGION;
 };
 
 // Mixing-head backward of one (episode, step), lanes = features
@@ -452,6 +496,15 @@ inline MixLaunch mix_pick(size_t wfl, size_t perw, int wmax_lds, int min_lds, in
     if (m.lds <= CAP) return m;
   }
   return MixLaunch{0, false, 0};
+}
+
+// Launch a mixer kernel with lds bytes of dynamic LDS (past the 64 KB default); the
+// launch's status.
+template <typename Kern, typename Args>
+inline int mix_launch(Kern kern, dim3 grid, int threads, size_t lds, hipStream_t stream, const Args& a) {
+  (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, a);
+  return (int)hipGetLastError();
 }
 
 }  // namespace t2o

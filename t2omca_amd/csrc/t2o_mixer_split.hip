@@ -496,16 +496,7 @@ T2O_DEV void mixs_rec_load(const MixsBwdArgs& sa, const MixerNet& n, int b, int 
     in.ph[k] = sa.pghw[(bt * 3 + k) * E + fl];
     in.ghx[k] = args.ghw_ext ? args.ghw_ext[(bt * 3 + k) * E + fl] : 0.f;
   }
-  const float* st = fa.states + b * fa.st_sb + t * fa.st_st;
-#pragma unroll
-  for (int s = 0; s < Dm::ST; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 16 * s + 4 * g + r;
-      float v = ld_or0(st, j * fa.Fs + c, j < na && c < fa.Fs);
-      if (j < na && c == fa.Fs) v = 1.f;
-      in.stT[s][r] = v;
-    }
+  mix_load_stT<E, A>(fa, b, t, in.stT, na);
   // (a step ahead: read-modify-written at the step's end, a dependent load there
   // would expose its latency on the recurrence)
 #pragma unroll
@@ -542,13 +533,7 @@ __global__ __launch_bounds__(256) void mixs_bwd_rec_kernel(MixsBwdArgs sa) {
   const int c = lane_c(), g = lane_g(), lane = threadIdx.x & 63;
   using Rec = TapeRec<E, H, FF>;
   const size_t nrec = (size_t)fa.B * T * nq, ctiles = (nrec + 15) / 16;
-  if (blockIdx.x == 0 && w == 0 && t_hi == T) {  // zero each block's compact stream past its last record
-    const int tail = (int)(ctiles * 16 - nrec) * Rec::SIZE;
-    for (int d = 0; d < D; ++d) {
-      WT* z = static_cast<WT*>(args.tape) + ((size_t)d * ctiles * 16 + nrec) * Rec::SIZE;
-      for (int i = lane; i < tail; i += 64) z[i] = WT(0.f);
-    }
-  }
+  if (blockIdx.x == 0 && w == 0 && t_hi == T) tape_zero_tail<D, Rec, WT>(args.tape, nrec);
   const int f = lane < E ? lane : 0;
   const bool fv = lane < E;
   f4 gWe[ET];
@@ -706,31 +691,9 @@ __global__ __launch_bounds__(256) void mixs_bwd_rec_kernel(MixsBwdArgs sa) {
 // 1 -> 0 (block-1 key grads in rows < lk, the grads wrt the block-1 input past
 // them), then the step's total key grads, whose hyper rows the block-1 wave reads
 // at its next backward phase.
+// (pair region: dW staging only, the window's 16 query rows handed over)
 template <int E, int A>
-struct MixsPipeDims {
-  using Dm = MixDims<E, A>;
-  using Bd = MixBwdDims<E, A>;
-  static constexpr int LDR = E;
-  static constexpr int XCH = Dm::LKCAP * LDR;  // window-row grads after the key rows
-  static constexpr int R0 = Bd::STAGE > Dm::KT * 16 * LDR ? Bd::STAGE : Dm::KT * 16 * LDR;
-  static constexpr int REGION = R0 > XCH + 16 * LDR ? R0 : XCH + 16 * LDR;
-  static constexpr int PAIRF = Dm::X0F + REGION;
-};
-
-template <int E, int A>
-T2O_DEV void mixs_load_stT(const MixerFwdArgs& fa, int b, int t, f4 (&stT)[MixDims<E, A>::ST], int na) {
-  const int c = lane_c(), g = lane_g();
-  const float* st = fa.states + b * fa.st_sb + t * fa.st_st;
-#pragma unroll
-  for (int s = 0; s < MixDims<E, A>::ST; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int j = 16 * s + 4 * g + r;
-      float v = ld_or0(st, j * fa.Fs + c, j < na && c < fa.Fs);
-      if (j < na && c == fa.Fs) v = 1.f;
-      stT[s][r] = v;
-    }
-}
+using MixsPipeDims = PairDims<E, A, MixBwdDims<E, A>::STAGE, 16>;
 
 template <int E, int H, int A, int FF, typename WT>
 T2O_DEV void mixs_pipe_block1(const MixsBwdArgs& sa, const Wts<WT>& P0, const t2o_layout& L, const t2o_layout& G,
@@ -840,7 +803,6 @@ T2O_DEV void mixs_pipe_block1(const MixsBwdArgs& sa, const Wts<WT>& P0, const t2
     vec_accumulate_g<ET>(gs + Gb.g2[0], &ln2[0]);
     vec_accumulate_g<ET>(gs + Gb.n2[0], &ln2[ET]);
   });
-  (void)G;
 }
 
 template <int E, int H, int A, int FF, typename WT>
@@ -873,7 +835,7 @@ T2O_DEV void mixs_pipe_block0(const MixsBwdArgs& sa, const Wts<WT>& P0, const t2
     f4 stT[Dm::ST], gh[HV];
     float ph[3];
     {  // ---- recompute: block-0 forward of the window rows (block inputs = X0 rows na + q)
-      mixs_load_stT<E, A>(fa, b, t, stT, na);
+      mix_load_stT<E, A>(fa, b, t, stT, na);
 #pragma unroll
       for (int k = 0; k < HV; ++k) gh[k] = ld4(args.ghid + bt * na * E + 4 * min(lane + 64 * k, na * E / 4 - 1));
 #pragma unroll
@@ -964,7 +926,6 @@ T2O_DEV void mixs_pipe_block0(const MixsBwdArgs& sa, const Wts<WT>& P0, const t2
     vec_accumulate_g<ET>(gs + Gb.g2[0], &ln2[0]);
     vec_accumulate_g<ET>(gs + Gb.n2[0], &ln2[ET]);
   });
-  (void)G;
 }
 
 template <int E, int H, int D, int A, int FF, int RT, typename WT>
@@ -988,15 +949,8 @@ __global__ __launch_bounds__(128) void mixs_bwd_rec_pipe_kernel(MixsBwdArgs sa) 
   for (int i = threadIdx.x; i < Dm::X0F; i += 128) X0[i] = 0.f;
   int* const flags = reinterpret_cast<int*>(R + Pd::REGION);
   if (threadIdx.x < PAIR_FLAG_FLOATS) flags[threadIdx.x] = 0;
-  if (blockIdx.x == 0 && threadIdx.x < 64 && sa.t_hi == T) {  // zero each block's compact stream past its last record
-    using Rec = TapeRec<E, H, FF>;
-    const size_t nrec = (size_t)args.f.B * T * (na + 3), ctiles = (nrec + 15) / 16;
-    const int tail = (int)(ctiles * 16 - nrec) * Rec::SIZE;
-    for (int dd = 0; dd < D; ++dd) {
-      WT* z = static_cast<WT*>(args.tape) + ((size_t)dd * ctiles * 16 + nrec) * Rec::SIZE;
-      for (int i = threadIdx.x; i < tail; i += 64) z[i] = WT(0.f);
-    }
-  }
+  if (blockIdx.x == 0 && threadIdx.x < 64 && sa.t_hi == T)
+    tape_zero_tail<D, TapeRec<E, H, FF>, WT>(args.tape, (size_t)args.f.B * T * (na + 3));
   __syncthreads();
   PairBarrier pb = PairBarrier::make(flags, w);
   const int b = blockIdx.x;
@@ -1040,25 +994,28 @@ inline int resident_grid(const void* kern, int threads, size_t lds, int want) {
   return want;
 }
 
+// How many waves of perw floats each fit beside the LDS weights (wfl floats): 8 / 4 /
+// 2, else 4 waves reading the weights through L2 (the caller checks that those fit).
+// Sets a.waves / a.wlds; the launch's LDS bytes.
+inline size_t mixs_fwd_fit(MixerFwdArgs& a, size_t wfl, size_t perw) {
+  for (a.waves = 8, a.wlds = 1; a.waves >= 2; a.waves >>= 1) {
+    const size_t lds = sizeof(float) * (wfl + a.waves * perw);
+    if (lds <= 160 * 1024) return lds;
+  }
+  a.waves = 4;
+  a.wlds = 0;
+  return sizeof(float) * 4 * perw;
+}
+
 template <int E, int H, int D, int A, int FF, int RT, typename WT>
 int mixs_launch_fwd(const MixerFwdArgs& args, int nnet, hipStream_t stream, int phase) {
-  using Dm = MixDims<E, A>;
   if (!kernel_layout_matches<E, H, D, FF, WT>(args.L)) return T2O_EINVAL;
   const size_t wfl = (lds_weight_floats<WT>(args.L, args.L.fwd_total) + 15) / 16 * 16;
   // recurrent part
   if (phase != 2) {
     MixerFwdArgs a = args;
     constexpr size_t perw = MixsFwdDims<E, A>::PERW;
-    size_t lds = 0;
-    for (a.waves = 8, a.wlds = 1; a.waves >= 2; a.waves >>= 1) {
-      lds = sizeof(float) * (wfl + a.waves * perw);
-      if (lds <= 160 * 1024) break;
-    }
-    if (a.waves < 2) {
-      a.waves = 4;
-      a.wlds = 0;
-      lds = sizeof(float) * 4 * perw;
-    }
+    size_t lds = mixs_fwd_fit(a, wfl, perw);
     // (small batches: fewer waves per workgroup spread the episodes over more CUs)
     while (a.waves > 1 && (args.B + a.waves - 1) / a.waves * nnet < 256) a.waves >>= 1;
     if (a.wlds) lds = sizeof(float) * (wfl + a.waves * perw);
@@ -1068,27 +1025,15 @@ int mixs_launch_fwd(const MixerFwdArgs& args, int nnet, hipStream_t stream, int 
                                : mixs_fwd_rec_kernel<E, H, D, A, FF, RT, false, WT, 256>)
                      : (a.wlds ? mixs_fwd_rec_kernel<E, H, D, A, FF, RT, true, WT>
                                : mixs_fwd_rec_kernel<E, H, D, A, FF, RT, false, WT>);
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3((args.B + a.waves - 1) / a.waves, nnet), dim3(64 * a.waves), lds, stream, a);
-    const int rc = (int)hipGetLastError();
+    const int rc = mix_launch(kern, dim3((args.B + a.waves - 1) / a.waves, nnet), 64 * a.waves, lds, stream, a);
     if (rc) return rc;
   }
   // every (episode, step)
   if (phase == 1) return 0;
   {
     MixerFwdArgs a = args;
-    constexpr size_t perw = MixsRowsDims<E, A>::PERW;
-    size_t lds = 0;
-    for (a.waves = 8, a.wlds = 1; a.waves >= 2; a.waves >>= 1) {
-      lds = sizeof(float) * (wfl + a.waves * perw);
-      if (lds <= 160 * 1024) break;
-    }
-    if (a.waves < 2) {
-      a.waves = 4;
-      a.wlds = 0;
-      lds = sizeof(float) * 4 * perw;
-      if (lds > 160 * 1024) return T2O_EUNSUPPORTED;
-    }
+    const size_t lds = mixs_fwd_fit(a, wfl, MixsRowsDims<E, A>::PERW);
+    if (lds > 160 * 1024) return T2O_EUNSUPPORTED;
     auto kern = a.wlds ? mixs_fwd_rows_kernel<E, H, D, A, FF, RT, true, WT> : mixs_fwd_rows_kernel<E, H, D, A, FF, RT, false, WT>;
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int tmax = args.net[0].T;
@@ -1147,10 +1092,7 @@ int mixs_launch_bwd(MixsBwdArgs& sa, int max_slabs, int* nslab, hipStream_t stre
       if (g2 + B > max_slabs) return T2O_EINVAL;
       *nslab = g2 + B;
       if (phase == 1) return 0;
-      auto kern = mixs_bwd_rec_pipe_kernel<E, H, D, A, FF, RT, WT>;
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kern, dim3(B), dim3(128), lds, stream, sa);
-      return (int)hipGetLastError();
+      return mix_launch(mixs_bwd_rec_pipe_kernel<E, H, D, A, FF, RT, WT>, dim3(B), 128, lds, stream, sa);
     }
   }
   {
@@ -1168,9 +1110,7 @@ int mixs_launch_bwd(MixsBwdArgs& sa, int max_slabs, int* nslab, hipStream_t stre
     *nslab = g2 + g1;
     if (phase == 1) return 0;
     auto kern = wlds ? mixs_bwd_rec_kernel<E, H, D, A, FF, RT, true, WT> : mixs_bwd_rec_kernel<E, H, D, A, FF, RT, false, WT>;
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(g1), dim3(64 * waves), lds, stream, sa);
-    return (int)hipGetLastError();
+    return mix_launch(kern, dim3(g1), 64 * waves, lds, stream, sa);
   }
 }
 

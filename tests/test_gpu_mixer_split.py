@@ -32,16 +32,24 @@ def _setup(A, B, T, precision, seed=5):
     return learner, batch, w
 
 
-def _with_split(flag, fn):
-    old = os.environ.get("T2O_MIXER_SPLIT")
-    os.environ["T2O_MIXER_SPLIT"] = flag
+def _with_env(name, flag, fn):
+    """fn() with the environment variable set to flag, or removed (flag None)."""
+    old = os.environ.get(name)
+    if flag is None:
+        os.environ.pop(name, None)
+    else:
+        os.environ[name] = flag
     try:
         return fn()
     finally:
         if old is None:
-            del os.environ["T2O_MIXER_SPLIT"]
+            os.environ.pop(name, None)
         else:
-            os.environ["T2O_MIXER_SPLIT"] = old
+            os.environ[name] = old
+
+
+def _with_split(flag, fn):
+    return _with_env("T2O_MIXER_SPLIT", flag, fn)
 
 
 @pytest.mark.parametrize("A,precision", [(16, "bf16"), (16, "fp32"), (20, "bf16"), (40, "fp32"), (64, "bf16")])
@@ -79,6 +87,90 @@ def test_split_mixer_equals_one_wave_kernels(A, precision):
     print(f"A={A} {precision} split vs one-wave backward:", {k: f"{v:.1e}" for k, v in errs.items()})
     bar = 1e-5 if precision == "fp32" else 2e-3
     assert max(errs.values()) < bar, errs
+
+
+def _split_forward(A, B, T, precision):
+    """One decoupled mixer forward (T2O_MIXER_SPLIT=1) and what its backward needs."""
+    from t2omca_amd import ops
+    learner, batch, w = _setup(A, B, T, precision)
+    sm, sa = learner.sm, learner.sa
+    ops.pack_params(sa, learner.params[:learner.na], learner.pack_a)
+    ops.pack_params(sm, learner.params[learner.na:], learner.pack_m)
+    state = batch["state"]
+    act = batch["actions"][..., 0].contiguous()
+    q_on, h_on = ops.agent_unroll_fwd(sa, learner.pack_a, batch["obs"])[:2]
+    gy = torch.randn(B, T, device="cuda", generator=torch.Generator("cuda").manual_seed(1))
+    o_on = _with_split("1", lambda: ops.mixer_unroll_fwd(sm, learner.pack_m, state, h_on, qmode_on=1, q_on=q_on,
+                                                         actions=act, T_on=T))
+    return learner, state, h_on, o_on, gy
+
+
+def _assert_rec_close(tag, precision, got, want):
+    (gp1, gqv1, gh1, gw1), (gp0, gqv0, gh0, gw0) = got, want
+    assert torch.equal(gqv1, gqv0), tag  # the rows kernel's: the same code in both runs
+    errs = {"ghid": normwise(gh1, gh0), "ghw0": normwise(gw1, gw0), "grads": normwise(gp1, gp0)}
+    print(f"{tag}:", {k: f"{v:.1e}" for k, v in errs.items()})
+    bar = 1e-5 if precision == "fp32" else 2e-3  # (a changed summation order, as above)
+    assert max(errs.values()) < bar, (tag, errs)
+
+
+@pytest.mark.parametrize("A,precision", [(16, "fp32"), (16, "bf16"), (20, "bf16")])
+def test_split_one_wave_recurrence_equals_pair_kernel(A, precision):
+    """T2O_MIXS_REC=single selects the one-wave mixs_bwd_rec_kernel where the pair
+    kernel (one wave per block) would run: after one forward, the two backwards agree —
+    dL/dqvals (the rows kernel, the same in both) bit for bit, the rest to rounding."""
+    require_gpu()
+    from t2omca_amd import ops
+    B, T = 5, 9
+    learner, state, h_on, o_on, gy = _split_forward(A, B, T, precision)
+
+    def run():
+        out = ops.mixer_unroll_bwd(learner.sm, learner.pack_m, state, h_on, o_on, gy, want_ghw0=True)
+        torch.cuda.synchronize()
+        return out
+
+    pair = _with_split("1", lambda: _with_env("T2O_MIXS_REC", None, run))  # the default: the pair kernel
+    single = _with_split("1", lambda: _with_env("T2O_MIXS_REC", "single", run))
+    _assert_rec_close(f"A={A} {precision} one-wave vs pair recurrence", precision, single, pair)
+    if (A, precision) == (16, "fp32"):
+        # the pair kernel's LDS fits here, so two different kernels ran: they sum the key
+        # gradients in another order and do not agree to the last bit
+        assert not (torch.equal(single[2], pair[2]) and torch.equal(single[0], pair[0])), "the switch selected nothing"
+
+
+def test_split_one_wave_recurrence_in_step_ranges():
+    """The one-wave recurrent kernel over steps (5, 9) then (0, 5) — the parallel part
+    first, the hyper grads carried between the ranges through `carry`, the same slabs,
+    tape and work buffers every call — against the same kernel over the whole unroll."""
+    require_gpu()
+    from t2omca_amd import ops
+    A, B, T, precision = 16, 5, 9, "fp32"
+    learner, state, h_on, o_on, gy = _split_forward(A, B, T, precision)
+    sm = learner.sm
+
+    def whole():
+        out = ops.mixer_unroll_bwd(sm, learner.pack_m, state, h_on, o_on, gy, want_ghw0=True)
+        torch.cuda.synchronize()
+        return out
+
+    def ranged():
+        L = sm.layout()
+        slabs = torch.empty(ops.mixer_slab_count(B) * L.grad_total, device="cuda")
+        tape = torch.empty(ops.tape_floats(sm, ops.mixer_tape_tiles(B, T, A, sm)), device="cuda")
+        work = torch.empty(ops.mixer_work_floats(sm, B, T), device="cuda")
+        carry = torch.zeros(B, 3, sm.E, device="cuda")
+        outs = (torch.empty(B, T, A, device="cuda"), torch.empty(B, T, A, sm.E, device="cuda"))
+        for phase, steps in ((1, None), (2, (5, 9)), (2, (0, 5))):
+            contract, gqv, ghid, ghw0 = ops.mixer_unroll_bwd(
+                sm, learner.pack_m, state, h_on, o_on, gy, want_ghw0=True, slabs=slabs, tape=tape, work=work,
+                phase=phase, steps=steps, carry=carry, outs=outs)
+        gpack = contract()
+        torch.cuda.synchronize()
+        return gpack, gqv, ghid, ghw0
+
+    one = _with_split("1", lambda: _with_env("T2O_MIXS_REC", "single", whole))
+    two = _with_split("1", lambda: _with_env("T2O_MIXS_REC", "single", ranged))
+    _assert_rec_close("one-wave recurrence in two step ranges vs one", precision, two, one)
 
 
 def test_split_learner_update_is_reproducible_and_close():
