@@ -62,6 +62,18 @@ constexpr int agent_fwd_waves_per_eu() { return NE <= 8 ? 2 : 1; }
 template <int NE, bool LEAN>
 constexpr int agent_fwd_wpe() { return agent_fwd_waves_per_eu<NE>() > 1 || LEAN ? 2 : 1; }
 
+// Weight fragments fetched one product ahead of their MFMA (wfrag_load,
+// t2o_common.hpp): the bf16 8-entity instances (exact and runtime capacity) with
+// the weights in LDS — one wave per SIMD, so nothing else covers the ds_read
+// latency between a product's reads and its first MFMA, and with registers to
+// spare under the 256 cap (tools/regs.sh, profiles/agent_wfrag/).  The other
+// instances keep the reads at their use: the 3-entity ones would drop from three
+// waves per SIMD to two (148 -> 173 VGPRs), 16+ entities have no registers left,
+// fp32 has four reads per MFMA step, and weights read through L2 are not
+// volatile reads to begin with.
+template <int NE, bool WLDS, typename WT>
+constexpr bool AGENT_FWD_WPF = sizeof(WT) == 2 && WLDS && NE == 8;
+
 // RT: runtime-entity instance (t2o_dispatch.hpp) — NE is a capacity, the real
 // entity count is args.A (n_entities = n_agents on the tuned path)
 template <int E, int H, int D, int NE, int FF, bool RT, bool WLDS, bool LOOP, typename WT, bool LEAN = false>
@@ -112,6 +124,7 @@ void agent_fwd_kernel(AgentFwdArgs args) {
     constexpr bool CHUNK = NE > AG_CHUNK_MIN;
     constexpr int NO = CHUNK ? 1 : NE;
     constexpr bool PF = !LEAN;
+    constexpr bool WPF = AGENT_FWD_WPF<NE, WLDS, WT>;
     auto row_obs = [&](int step) {
       return args.obs + b * args.obs_sb + step * args.obs_st + (int64_t)a * ne * F;
     };
@@ -127,6 +140,14 @@ void agent_fwd_kernel(AgentFwdArgs args) {
     };
     f4 on[PF ? NO : 1];
     if constexpr (!CHUNK && PF) load_obs(args.t0, on);
+    // WPF: the weight fragments of each product's first tile are fetched one
+    // product ahead (agent_block_fwd_pf), across the step boundary too: the head
+    // tile of block 0's M is in flight when a step begins (the weights do not
+    // change over t; the fetch after the last step reads the same LDS image)
+    [[maybe_unused]] AgentFwdPf<E, H> wpf;
+    [[maybe_unused]] WFrag<ET> wof;
+    [[maybe_unused]] f4 bov;
+    if constexpr (WPF) wfrag_load<ET>(P0.w + L.M[0], E, 0, wpf.m, P0.vol);
     for (int step = args.t0; step < args.t1; ++step) {
       const Wts<WT> P = step_view(P0);
       f4 o[NO];
@@ -150,15 +171,32 @@ void agent_fwd_kernel(AgentFwdArgs args) {
         }
         if constexpr (CHUNK) {
           agent_block_fwd_ch<E, H, NE, FF, false>(P, L, d, h, orow, x, nullptr);
+        } else if constexpr (WPF) {
+          (void)orow;
+          agent_block_fwd_pf<E, H, NE, FF>(P, L, d, h, o, ne, x, wpf, [&] {
+            if (d + 1 < D) {
+              wfrag_load<ET>(P.w + L.M[d + 1], E, 0, wpf.m, P.vol);
+            } else {  // the Q head's fragments and the next step's first product
+              wfrag_load<ET>(P.w + L.Wo, E, 0, wof, P.vol);
+              wfrag_load<ET>(P.w + L.M[0], E, 0, wpf.m, P.vol);
+              bov = vec_t(P.v + L.bo, 0);
+            }
+          });
         } else {
           (void)orow;
           agent_block_fwd<E, H, NE, FF, false>(P, L, d, h, o, ne, x, nullptr);
         }
       }
       f4 q = zero4();
+      if constexpr (WPF) {
 #pragma unroll
-      for (int i = 0; i < ET; ++i) q = mma_tile(P.w + L.Wo, E, 0, i, x[i], q, P.vol);
-      q += vec_t(P.v + L.bo, 0);
+        for (int i = 0; i < ET; ++i) q = mfma_b16(wof.f[i], to_bf4(x[i]), q);
+        q += bov;
+      } else {
+#pragma unroll
+        for (int i = 0; i < ET; ++i) q = mma_tile(P.w + L.Wo, E, 0, i, x[i], q, P.vol);
+        q += vec_t(P.v + L.bo, 0);
+      }
 #pragma unroll
       for (int t = 0; t < ET; ++t) h[t] = x[t];
       if (valid) {

@@ -51,22 +51,66 @@ using AgentCacheLean = AgentCacheT<E, H, NE, FF, true>;
 // z_h = p0 h + We ô_h + P_h b_e.  Caches (u, p, ô, P) when C is non-null.
 // ne: the entity count (NE, or fewer in a runtime-entity instance: entities
 // j >= ne are padding — zero observations, score -inf, probability 0).
-template <int E, int H, int NE, int FF, bool LEAN, typename WT>
+// PF (bf16, weights in LDS; pf non-null): weight fragments fetched ahead of
+// their MFMAs (wfrag_load, t2o_common.hpp).  pf->m holds M's head tile, fetched
+// by the caller under the previous block's LN2; the fragments of Weᵀ and We,
+// which every head shares, are fetched once under M's MFMAs; N's head tile is
+// fetched under the last head's softmax and returned in pf->n.
+template <int E, int H>
+struct AgentFwdPf {
+  WFrag<E / 16> m;
+  WFrag<H * (E / 16)> n;
+  f4 bu[E / 16];  // N's bias, read beside its head tile
+};
+template <int E, int H, int NE, int FF, bool LEAN, typename WT, bool PF = false>
 T2O_DEV void agent_attn_fwd(const Wts<WT>& P, const t2o_layout& L, int d, const f4* h, const f4 (&o)[NE], int ne,
-                            const f4* x, f4* z, AgentCacheT<E, H, NE, FF, LEAN>* cache) {
+                            const f4* x, f4* z, AgentCacheT<E, H, NE, FF, LEAN>* cache,
+                            AgentFwdPf<E, H>* pf = nullptr) {
   constexpr int ET = E / 16, HET = H * ET, NB = agent_nb<NE>();
   const float* be = P.v + L.be;
   const int g = lane_g();
   f4 u[HET];
-  matvec<HET, ET>(P.w + L.M[d], E, x, u, P.vol);
+  WFrag<ET> wet;
+  WFrag<1> we[ET];
+  [[maybe_unused]] f4 bet[ET];
+  if constexpr (PF) {
+    bf4 xb[ET];
+#pragma unroll
+    for (int i = 0; i < ET; ++i) xb[i] = to_bf4(x[i]);
+    wfrag_load<ET>(P.w + L.WeT, E, 0, wet, P.vol);
+#pragma unroll
+    for (int t = 0; t < ET; ++t) wfrag_load<1>(P.w + L.We, 16, t, we[t], P.vol);
+#pragma unroll
+    for (int t = 0; t < ET; ++t) bet[t] = vec_t(be, t);
+    matvec_b<HET, ET>(P.w + L.M[d], E, pf->m, xb, u, P.vol);
+  } else {
+    matvec<HET, ET>(P.w + L.M[d], E, x, u, P.vol);
+  }
+  auto be_t = [&](int t) {  // (PF: read once, beside the fragments)
+    if constexpr (PF) return bet[t];
+    else return vec_t(be, t);
+  };
 #pragma unroll
   for (int hh = 0; hh < H; ++hh) {
     f4 w;
-    matvec<1, ET>(P.w + L.WeT, E, &u[hh * ET], &w, P.vol);
+    if constexpr (PF) {
+      bf4 ub[ET];
+#pragma unroll
+      for (int i = 0; i < ET; ++i) ub[i] = to_bf4(u[hh * ET + i]);
+      w = wfrag_tile<ET>(wet, ub, zero4());
+      if (hh == H - 1) {
+        wfrag_load<HET>(P.w + L.N[d], HET * 16, 0, pf->n, P.vol);
+#pragma unroll
+        for (int t = 0; t < ET; ++t) pf->bu[t] = vec_t(P.v + L.bu[d], t);
+        wfrag_pin();
+      }
+    } else {
+      matvec<1, ET>(P.w + L.WeT, E, &u[hh * ET], &w, P.vol);
+    }
     float cpart = 0.f, s0part = 0.f;
 #pragma unroll
     for (int t = 0; t < ET; ++t) {
-      const f4 bt = vec_t(be, t);
+      const f4 bt = be_t(t);
       const f4 ut = u[hh * ET + t];
       cpart += dot4_pk(ut, bt);
       s0part += dot4_pk(ut, h[t]);
@@ -106,9 +150,15 @@ T2O_DEV void agent_attn_fwd(const Wts<WT>& P, const t2o_layout& L, int d, const 
 #pragma unroll
     for (int j = 0; j < NE; ++j) oh += pa[j] * o[j];
     f4 zz[ET];
-    matvec<ET, 1>(P.w + L.We, 16, &oh, zz, P.vol);
+    if constexpr (PF) {
+      const bf4 ob = to_bf4(oh);
 #pragma unroll
-    for (int t = 0; t < ET; ++t) z[hh * ET + t] = zz[t] + p0 * h[t] + Ps * vec_t(be, t);
+      for (int t = 0; t < ET; ++t) zz[t] = wfrag_tile<1>(we[t], &ob, zero4());
+    } else {
+      matvec<ET, 1>(P.w + L.We, 16, &oh, zz, P.vol);
+    }
+#pragma unroll
+    for (int t = 0; t < ET; ++t) z[hh * ET + t] = zz[t] + p0 * h[t] + Ps * be_t(t);
     if (cache) {
       cache->oh[hh] = oh;
       cache->Ps[hh] = Ps;
@@ -133,6 +183,20 @@ T2O_DEV void agent_block_fwd(const Wts<WT>& P, const t2o_layout& L, int d, const
   agent_attn_fwd<E, H, NE, FF, false>(P, L, d, h, o, ne, x, z, CACHE ? cache : nullptr);
   T2O_MARK(2);
   post_fwd<E, H, FF, CACHE>(P, L, d, z, x, CACHE ? &cache->post : nullptr);
+}
+
+// agent_block_fwd without a cache, fragments fetched ahead (agent_attn_fwd PF,
+// post_fwd_pf).  pf.m: in, the head tile of this block's M; next(): the caller's
+// fetch for the product after the block (the next block's or step's M, the Q
+// head), issued under LN2.
+template <int E, int H, int NE, int FF, typename Next>
+T2O_DEV void agent_block_fwd_pf(const Wts<__bf16>& P, const t2o_layout& L, int d, const f4* h, const f4 (&o)[NE],
+                                int ne, f4* x, AgentFwdPf<E, H>& pf, Next&& next) {
+  constexpr int HET = H * (E / 16);
+  f4 z[HET];
+  agent_attn_fwd<E, H, NE, FF, false, __bf16, true>(P, L, d, h, o, ne, x, z, nullptr, &pf);
+  T2O_MARK(2);
+  post_fwd_pf<E, H, FF>(P, L, d, z, x, pf.n, pf.bu, next);
 }
 
 template <int E, int H, int NE, int FF, typename WT>

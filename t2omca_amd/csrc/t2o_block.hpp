@@ -123,6 +123,64 @@ T2O_DEV void post_fwd(const Wts<WT>& P, const t2o_layout& L, int d, const f4* z,
   }
 }
 
+// post_fwd (bf16, no cache) with every product's head fragments fetched one
+// product ahead (wfrag_load, t2o_common.hpp): N's by the caller (nh, with the
+// bias bu), W1's under LN1, W2's under W1's MFMAs and the ReLU / conversion, and
+// `next` — the caller's fetch for the product that follows the block — under
+// LN2.  The bias and LayerNorm vectors, LDS reads as well, are read beside the
+// fragments for the same reason.  The same MFMAs on the same operands as
+// ffn_half / ffn_tail.
+template <int E, int H, int FF, typename Next>
+T2O_DEV void post_fwd_pf(const Wts<__bf16>& P, const t2o_layout& L, int d, const f4* z, f4* x,
+                         const WFrag<H * (E / 16)>& nh, const f4* bu, Next&& next) {
+  constexpr int ET = E / 16, HET = H * ET, FT = FF / 16;
+  static_assert(FT % 2 == 0, "FFN tiles convert in pairs");
+  f4 r1[ET], y[ET], xh1[ET], f1[FT], r2[ET], xh2[ET], ga[ET], be[ET];
+  float rs1, rs2;
+  bf4 zb[HET], yb[ET], fb[FT];
+#pragma unroll
+  for (int t = 0; t < ET; ++t) r1[t] = bu[t] + x[t];
+#pragma unroll
+  for (int i = 0; i < HET; ++i) zb[i] = to_bf4(z[i]);
+  matvec_b<ET, HET, T2O_SWZ_HOIST, true>(P.w + L.N[d], HET * 16, nh, zb, r1, P.vol);
+  WFrag<ET> w1h;
+  wfrag_load<ET>(P.w + L.W1[d], ET * 16, 0, w1h, P.vol);
+#pragma unroll
+  for (int t = 0; t < ET; ++t) {
+    ga[t] = vec_t(P.v + L.g1[d], t);
+    be[t] = vec_t(P.v + L.n1[d], t);
+  }
+#pragma unroll
+  for (int t = 0; t < FT; ++t) f1[t] = vec_t(P.v + L.c1[d], t);
+  wfrag_pin();
+  layernorm_fwd<ET>(r1, ga, be, y, xh1, rs1);
+#pragma unroll
+  for (int i = 0; i < ET; ++i) yb[i] = to_bf4(y[i]);
+  matvec_b<FT, ET, T2O_SWZ_HOIST, true>(P.w + L.W1[d], ET * 16, w1h, yb, f1, P.vol);
+  WFrag<FT> w2h;
+  wfrag_load<FT>(P.w + L.W2[d], FT * 16, 0, w2h, P.vol);
+#pragma unroll
+  for (int t = 0; t < ET; ++t) r2[t] = vec_t(P.v + L.c2[d], t);
+  wfrag_pin();
+#pragma unroll
+  for (int t = 0; t < ET; ++t) r2[t] += y[t];
+#pragma unroll
+  for (int t = 0; t < FT; t += 2) {
+    const bf8 v = relu_bf8(cvt8(f1[t], f1[t + 1]));
+    fb[t] = lo4(v);
+    fb[t + 1] = hi4(v);
+  }
+  matvec_b<ET, FT, T2O_SWZ_HOIST, true>(P.w + L.W2[d], FT * 16, w2h, fb, r2, P.vol);
+  next();
+#pragma unroll
+  for (int t = 0; t < ET; ++t) {
+    ga[t] = vec_t(P.v + L.g2[d], t);
+    be[t] = vec_t(P.v + L.n2[d], t);
+  }
+  wfrag_pin();
+  layernorm_fwd<ET>(r2, ga, be, x, xh2, rs2);
+}
+
 // gx: grad wrt block output.  Produces gz (grad wrt z, HET tiles) and gres
 // (grad wrt the block input through the LN1 residual).  The operands of the
 // big weight grads (N, W1, W2) and of the bu / c1 / c2 / g1 / n1 grads go to

@@ -339,6 +339,53 @@ T2O_DEV void matvec_b(const __bf16* __restrict__ W, int ldw, const bf4* xb, f4* 
   }
 }
 
+// The product in two halves, so that a one-wave-per-SIMD kernel can issue a
+// product's weight reads ahead of the VALU section (LayerNorm, softmax,
+// conversion) that produces its B operand instead of stalling on them at the
+// first MFMA: wfrag_load fetches the A operands of one output tile,
+// wfrag_tile contracts them.  The reads, the MFMAs, their operands and the
+// accumulation chain are matvec_b's own, so the split is bit-identical.
+template <int IT>
+struct WFrag {
+  bf4 f[IT];
+};
+template <int IT, bool HOIST = T2O_SWZ_HOIST>
+T2O_DEV void wfrag_load(const __bf16* __restrict__ W, int ldw, int o, WFrag<IT>& F, bool vol = true) {
+  int l = threadIdx.x;
+  if (!HOIST) asm volatile("" : "+v"(l));  // (see matvec_b)
+  const int c = l & 15, g = (l >> 4) & 3;
+  const int xs = bf_swz(c, ldw);
+  const __bf16* row = W + (size_t)(16 * o + c) * ldw;
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const __bf16* p = row + ((16 * i + 4 * g) ^ xs);
+    F.f[i] = vol ? ldw4(p) : ldb4(p);
+  }
+}
+// hipcc's scheduler sinks an early read back down to its MFMA (it minimises
+// live registers); a scheduling barrier after the fetch keeps it where it is.
+T2O_DEV void wfrag_pin() { __builtin_amdgcn_sched_barrier(0); }
+template <int IT>
+T2O_DEV f4 wfrag_tile(const WFrag<IT>& F, const bf4* xb, f4 acc) {
+#pragma unroll
+  for (int i = 0; i + 1 < IT; i += 2) acc = mfma_b32(F.f[i], F.f[i + 1], xb[i], xb[i + 1], acc);
+  if constexpr (IT & 1) acc = chain_tail_b16<(IT > 1)>(F.f[IT - 1], xb[IT - 1], acc);
+  return acc;
+}
+// matvec_b with output tile 0's fragments fetched by the caller (wfrag_load(W,
+// ldw, 0, head), issued one product ahead).  Only tile 0 has exposed latency, so the
+// remaining tiles' reads are issued here, before the first MFMA.
+template <int OT, int IT, bool HOIST = T2O_SWZ_HOIST, bool ACC = false>
+T2O_DEV void matvec_b(const __bf16* __restrict__ W, int ldw, const WFrag<IT>& head, const bf4* xb, f4* y,
+                      bool vol = true) {
+  WFrag<IT> rest[OT > 1 ? OT - 1 : 1];
+#pragma unroll
+  for (int o = 1; o < OT; ++o) wfrag_load<IT, HOIST>(W, ldw, o, rest[o - 1], vol);
+  if constexpr (OT > 1) wfrag_pin();
+#pragma unroll
+  for (int o = 0; o < OT; ++o) y[o] = wfrag_tile<IT>(o ? rest[o - 1] : head, xb, ACC ? y[o] : zero4());
+}
+
 // The kernels' weight view: matrices (fp32 or bf16) and vectors (always fp32).
 template <typename WT>
 struct Wts {
@@ -637,6 +684,30 @@ T2O_DEV void layernorm_fwd(const f4* r, const float* __restrict__ gamma,
   for (int t = 0; t < ET; ++t) {
     xhat[t] = (r[t] - mean) * rstd;
     out[t] = xhat[t] * vec_t(gamma, t) + vec_t(beta, t);
+  }
+}
+
+// ... with gamma / beta slices the caller read ahead (vec_t), beside its weight
+// fragments: the same arithmetic
+template <int ET>
+T2O_DEV void layernorm_fwd(const f4* r, const f4* gamma, const f4* beta, f4* out, f4* xhat, float& rstd) {
+  constexpr float inv_e = 1.0f / (16 * ET);
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < ET; ++t) s += (r[t][0] + r[t][1]) + (r[t][2] + r[t][3]);
+  const float mean = allsum4(s) * inv_e;
+  float v = 0.f;
+#pragma unroll
+  for (int t = 0; t < ET; ++t) {
+    const f4 d = r[t] - mean;
+    v += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+  }
+  const float var = allsum4(v) * inv_e;
+  rstd = rsqrt_fast(var + 1e-5f);
+#pragma unroll
+  for (int t = 0; t < ET; ++t) {
+    xhat[t] = (r[t] - mean) * rstd;
+    out[t] = xhat[t] * gamma[t] + beta[t];
   }
 }
 
