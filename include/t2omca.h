@@ -33,6 +33,29 @@
  *   - return 0 on success, a negative T2O_E* code on a bad argument, or the
  *     positive hipError_t of a failed launch;
  *   - float tensors are fp32, row-major, contiguous unless a stride is given.
+ *
+ * Memory contract (tests/test_gpu_memory_contract.py holds every entry point to it
+ * on tensors carved from a poisoned arena, tests/arena.py):
+ *   - strides are in ELEMENTS of the tensor's type, positive, and apply to the two
+ *     leading axes only (episode b, step t): what lies inside one (b, t) — [a][...] —
+ *     is dense.  sb < st (time-major storage viewed [b][t]) and sb > T * st (a
+ *     [:, :T] slice of a longer, padded slab) are both fine; rows must not overlap;
+ *   - a kernel never USES a value outside the logical elements [0, B) x [t range]
+ *     of a strided input (loads of padding lanes / rows are clamped to in-bounds
+ *     duplicates), so the memory between the rows of a view and past its last step
+ *     may hold anything, NaNs included;
+ *   - a kernel never WRITES outside the stated size of an output or a workspace:
+ *     the sizes given here (t2o_bwd_tape_floats, t2o_*_bwd_max_slabs x grad_total,
+ *     t2o_mixer_bwd_work_floats, t2o_adam_workspace_floats,
+ *     t2o_per_workspace_doubles, t2o_noisy_head_parts, pack_floats) are exact, no
+ *     slack is needed behind them.  Partial 16-row tiles mask their stores;
+ *   - alignment: every float pointer is 16-byte aligned where the kernels move whole
+ *     4-float groups — all dense float outputs, workspaces, packs, h0 / h_seq / hmid /
+ *     gh / gcarry, hw / xout / xmid, and the mixers' strided hid_on / hid_tg / hid,
+ *     whose hid_sb / hid_st are therefore multiples of 4 floats (T2O_EINVAL
+ *     otherwise).  obs, states, reward and the q / qv arrays are read element-wise:
+ *     4-byte alignment and any strides; actions 8-byte (int64), avail 4-byte (int32),
+ *     masks their element's size.
  */
 #ifndef T2OMCA_H
 #define T2OMCA_H
@@ -254,7 +277,8 @@ typedef struct {
   int64_t st_sb, st_st;
   const float* hid_on;        /* agent hidden states [b][t][a][E], strides hid_sb, hid_st, a-stride E */
   const float* hid_tg;
-  int64_t hid_sb, hid_st;
+  int64_t hid_sb, hid_st;     /* tuned kernels load 4 floats at a time: hid_on / hid_tg 16-byte aligned,
+                                 hid_sb (B > 1) and hid_st (T > 1) multiples of 4, else T2O_EINVAL */
   const float* hw0_on;        /* initial hyper tokens [B][3][E]; NULL = zeros */
   const float* hw0_tg;
   int32_t qmode_on, qmode_tg;
@@ -296,7 +320,7 @@ typedef struct {
   const float* states;
   int64_t st_sb, st_st;
   const float* hid;
-  int64_t hid_sb, hid_st;
+  int64_t hid_sb, hid_st;     /* aligned as the forward's (T2O_EINVAL otherwise) */
   const float* hw0;
   const float* qv;            /* forward qvo [B][T][A] */
   const float* hw;            /* forward hw */

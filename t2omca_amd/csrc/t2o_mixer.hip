@@ -832,6 +832,12 @@ int launch_mixer_bwd(MixerBwdArgs& args, int max_slabs, int* nslab, hipStream_t 
 // diagnostic builds only (-DT2O_PHASE_PROF, tools/phase_prof.py)
 T2O_PROF_READER(t2o_prof_read_mixer)
 
+// The tuned kernels read a step's hidden tokens with 16-byte loads (mix_load): the
+// base and every (episode, step) row must be 16-byte aligned (include/t2omca.h).
+static bool hid_rows_aligned(const float* hid, int64_t hid_sb, int64_t hid_st, int B, int T) {
+  return (reinterpret_cast<uintptr_t>(hid) & 15) == 0 && (B < 2 || hid_sb % 4 == 0) && (T < 2 || hid_st % 4 == 0);
+}
+
 static int mixer_fwd_impl(const t2o_layout* L, const float* pack_on, const float* pack_tg,
                           const float* states, int64_t st_sb, int64_t st_st,
                           const float* hid_on, const float* hid_tg, int64_t hid_sb, int64_t hid_st,
@@ -857,6 +863,9 @@ static int mixer_fwd_impl(const t2o_layout* L, const float* pack_on, const float
                                 act_sb, act_st, avail, av_sb, av_st, y_on, hw_on, qvo_on, xout_on, xmid_on, y_tg,
                                 hw_tg, qvo_tg, xout_tg, xmid_tg, B, T_on, T_tg, (hipStream_t)stream);
   }
+  if (!hid_rows_aligned(hid_on, hid_sb, hid_st, B, T_on) ||
+      (pack_tg && hid_tg && !hid_rows_aligned(hid_tg, hid_sb, hid_st, B, T_tg)))
+    return T2O_EINVAL;
   MixerFwdArgs a{};
   a.L = *L;
   a.states = states;
@@ -945,6 +954,7 @@ static int mixer_bwd_impl(const t2o_layout* L, const float* pack, const float* s
     return gen_mixer_unroll_bwd(L, pack, states, st_sb, st_st, hid, hid_sb, hid_st, hw0, qv, hw, xout, xmid, gy,
                                 ghw_ext, gqv, ghid, ghw0, gslabs, max_slabs, nslab, tape, B, T, (hipStream_t)stream);
   }
+  if (!hid_rows_aligned(hid, hid_sb, hid_st, B, T)) return T2O_EINVAL;
   MixerBwdArgs a{};
   a.f.L = *L;
   a.f.states = states;

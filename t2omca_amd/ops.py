@@ -300,6 +300,14 @@ def _mstrides(t):
     return (t.stride(0), t.stride(1)) if t is not None else (0, 0)
 
 
+def _hid_aligned(hid):
+    """include/t2omca.h (t2o_mixer_fwd_args.hid_on): the mixer kernels read a step's hidden
+    tokens with 16-byte loads, so the base and every (episode, step) row are 16-byte
+    aligned: episode / step strides in multiples of 4 floats."""
+    return (hid.data_ptr() % 16 == 0 and (hid.shape[0] < 2 or hid.stride(0) % 4 == 0) and
+            (hid.shape[1] < 2 or hid.stride(1) % 4 == 0))
+
+
 def mixer_unroll_fwd(shape: NetShape, pack_on, states, hid_on, *, qmode_on=0, qv_on=None, q_on=None,
                      actions=None, avail=None, hw0_on=None, T_on=None,
                      pack_tg=None, hid_tg=None, qmode_tg=2, qv_tg=None, q_tg=None, hw0_tg=None,
@@ -319,8 +327,10 @@ def mixer_unroll_fwd(shape: NetShape, pack_on, states, hid_on, *, qmode_on=0, qv
     dev = states.device
     T_on = T_on or (qv_on.shape[1] if qv_on is not None else hid_on.shape[1])
     assert hid_on.stride(3) == 1 and hid_on.stride(2) == E and states.stride(2) == 1
+    assert _hid_aligned(hid_on), "mixer_unroll_fwd: hidden-state rows must be 16-byte aligned"
     if hid_tg is not None:
         assert hid_tg.stride(0) == hid_on.stride(0) and hid_tg.stride(1) == hid_on.stride(1)
+        assert _hid_aligned(hid_tg), "mixer_unroll_fwd: hidden-state rows must be 16-byte aligned"
     q_ts = q_on.shape[1] if q_on is not None else 0
     for q in (q_on, q_tg):
         assert q is None or (q.is_contiguous() and q.shape[1] == q_ts)
@@ -435,6 +445,7 @@ def mixer_unroll_bwd(shape: NetShape, pack, states, hid, fwd, gy, hw0=None, ghw_
     L = shape.layout()
     dev = gy.device
     assert gy.is_contiguous() and fwd["xout"] is not None
+    assert _hid_aligned(hid), "mixer_unroll_bwd: hidden-state rows must be 16-byte aligned"
     nmax = int(lib().t2o_mixer_bwd_max_slabs(B))
     if slabs is None or slabs.numel() < nmax * L.grad_total:
         nmax = mixer_slab_count(B)
