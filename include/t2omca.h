@@ -23,6 +23,7 @@
  *   t2o_td_qlambda         t2o_td_loss with Peng's Q(λ) targets (q_lambda: True)
  *   t2o_rmsprop_step       the RMSprop optimiser step (optimizer != 'adam')
  *   t2o_noise_normal / t2o_noisy_head_*  the NoisyLinear Q head (action_selector: noisy-new)
+ *   t2o_q_select / t2o_qmix_* / t2o_vdn_bwd  the QMIX and VDN mixers (mixer: qmix, vdn)
  *   t2o_env_step / reset   MultiAgvOffloadingEnv.step/reset/get_obs/get_state
  *                          (environment_multi_mec.py:184-366, normalization.py)
  *
@@ -197,6 +198,10 @@ int t2o_unpack_grads(const t2o_layout* L, const float* params, const float* gpac
 #define T2O_ARGS_NOISY_FWD 9
 #define T2O_ARGS_NOISY_BWD 10
 #define T2O_ARGS_NOISY_WGRAD 11
+/* (12 stays unassigned: it was published as the first unknown id, for which t2o_args_sizeof gives -1) */
+#define T2O_ARGS_Q_SELECT 13
+#define T2O_ARGS_QMIX_FWD 14
+#define T2O_ARGS_QMIX_BWD 15
 int t2o_args_sizeof(int which); /* sizeof the T2O_ARGS_* struct, -1 for an unknown one */
 
 /* Agent unroll forward (TransformerAgent.forward over t, transf_agent.py:54-76) for
@@ -625,6 +630,96 @@ typedef struct {
   int32_t reserved_;
 } t2o_noisy_wgrad_args;
 int t2o_noisy_head_wgrad(const t2o_noisy_wgrad_args* a, void* stream);
+
+/* ---- the QMIX and VDN mixers (t2o_qmix.hip; TDLearner with mixer: qmix / vdn).
+ * Neither ships with the reference (n_transf_mixer.py only): they are DECLARED
+ * definitions after PyMARL2's modules/mixers/nmix.py and vdn.py (parity-unpinned,
+ * DESIGN.md §5).  Per (episode, step) row, with state s [S] and the agents' q [A]:
+ *   w1 = pos(hyper_w1(s)).view(A, M)   hyper_w1 = Linear(S, H), ReLU, Linear(H, A·M)
+ *   b1 = hyper_b1(s)                   hyper_b1 = Linear(S, M)
+ *   w2 = pos(hyper_w2(s))              hyper_w2 = Linear(S, H), ReLU, Linear(H, M)
+ *   b2 = hyper_b2(s)                   hyper_b2 = Linear(S, M), ReLU, Linear(M, 1)
+ *   y  = elu(q · w1 + b1) · w2 + b2
+ * Parameters are read straight from a flat buffer in that registration order (each
+ * Linear its weight [out][in], then its bias): t2o_qmix_param_count floats.  All
+ * arithmetic is fp32.  Limits: 1 <= A <= 64, 1 <= S <= 1024, M in {16, 32}, H in
+ * {32, 64}, B·T < 2^27, pos_func one of T2O_POS_*.  (Added within ABI 6: nothing existing moved.)
+ * T2O_EINVAL for a null required pointer or a bad size, before any launch; no
+ * allocation, no synchronisation, no atomics. */
+
+/* The learner's chosen-Q gather and double-Q selection, for up to two networks in
+ * one launch (the first over t < T_on, the second over t < T_tg), with the qmode
+ * meanings, strides and tie rule of t2o_mixer_unroll_fwd: 1 = the network's Q at
+ * `actions`; 2 = the network's Q at the argmax over actions of q_on masked by
+ * `avail` (NULL: all available; ties -> the lowest index).  The first network reads
+ * q_on, the second q_tg.  y_* (optional) = Σ_a qv: VDN's forward. */
+typedef struct {
+  const float* q_on;          /* [b][q_ts][a][n_actions], dense; also the argmax's source (qmode 2) */
+  const float* q_tg;          /* NULL: one network */
+  int32_t q_ts, n_actions;
+  const int64_t* actions;     /* [b][t][a], strides act_sb, act_st (qmode 1) */
+  int64_t act_sb, act_st;
+  const int32_t* avail;       /* [b][t][a][n_actions], strides av_sb, av_st, or NULL */
+  int64_t av_sb, av_st;
+  int32_t qmode_on, qmode_tg; /* 1 or 2 */
+  float* qv_on;               /* out [B][T_on][A] */
+  float* qv_tg;               /* out [B][T_tg][A] */
+  float* y_on;                /* out [B][T_on] or NULL */
+  float* y_tg;                /* out [B][T_tg] or NULL */
+  int32_t B, T_on, T_tg, A;
+} t2o_q_select_args;
+int t2o_q_select(const t2o_q_select_args* a, void* stream);
+
+int64_t t2o_qmix_param_count(int A, int S, int M, int H); /* T2O_EINVAL on a size outside the limits */
+
+/* QMIX forward of up to two networks in one launch on rows (b, t < T_*). */
+typedef struct {
+  const float* params_on;
+  const float* params_tg;     /* NULL: one network */
+  const float* states;        /* [b][t][S], element strides st_sb, st_st */
+  int64_t st_sb, st_st;
+  const float* qv_on;         /* [B][T_on][A] */
+  const float* qv_tg;         /* [B][T_tg][A] */
+  float* y_on;                /* out [B][T_on] */
+  float* y_tg;                /* out [B][T_tg] */
+  int32_t B, T_on, T_tg;
+  int32_t A, S, M, H;
+  int32_t pos_func;           /* T2O_POS_* */
+  float pos_beta;
+  int32_t reserved_;
+} t2o_qmix_fwd_args;
+int t2o_qmix_fwd(const t2o_qmix_fwd_args* a, void* stream);
+
+/* QMIX backward of one network.  It recomputes the forward.  phase 1: every row's
+ * dL/dqv into gqv and the row's small activations (4H + 4M + 4 floats) into work;
+ * phase 2: the weight gradients from work, as t2o_qmix_bwd_slabs(B, T) partial
+ * slabs [nslab][t2o_qmix_param_count] in the parameter order, each element written
+ * once by one workgroup in a fixed order (sum them with t2o_reduce_slabs).  phase 0:
+ * both, in order.  w1 [rows][A·M] is never written to memory: phase 2 recomputes it
+ * per agent chunk. */
+typedef struct {
+  const float* params;
+  const float* states;
+  int64_t st_sb, st_st;
+  const float* qv;            /* [B][T][A] */
+  const float* gy;            /* dL/dy [B][T] */
+  float* gqv;                 /* out [B][T][A] */
+  float* gslabs;              /* out [>= t2o_qmix_bwd_slabs][t2o_qmix_param_count] */
+  float* work;                /* t2o_qmix_bwd_work_floats floats, 16-byte aligned */
+  int64_t work_floats;
+  int32_t max_slabs;
+  int32_t phase;
+  int32_t B, T;
+  int32_t A, S, M, H;
+  int32_t pos_func;
+  float pos_beta;
+} t2o_qmix_bwd_args;
+int t2o_qmix_bwd(const t2o_qmix_bwd_args* a, void* stream);
+int t2o_qmix_bwd_slabs(int B, int T);                       /* T2O_EINVAL on a bad size */
+int64_t t2o_qmix_bwd_work_floats(int B, int T, int M, int H);
+
+/* VDN backward: gqv[b][t][a] = gy[b][t]. */
+int t2o_vdn_bwd(const float* gy, float* gqv, int B, int T, int A, void* stream);
 
 /* Diagnostic: runs the cross-lane primitives the kernels rely on (4-lane
  * all-reduces via ds_bpermute and via gfx950 permlane swaps, 16-lane DPP row

@@ -90,8 +90,15 @@ NoisyBwdArgs = _args_class("NoisyBwdArgs", 10, """gchosen:P, actions:P, act_sb:J
     eps_w:P, gh_in:P, gh_out:P, gpart:P, h_ts:I, B:I, T:I, A:I, E:I, NA:I, t_lo:I, t_hi:I""")
 NoisyWgradArgs = _args_class("NoisyWgradArgs", 11, """gpart:P, eps_w:P, eps_b:P, du_w:P, du_b:P, ds_w:P, ds_b:P,
     B:I, T:I, A:I, E:I, NA:I, reserved_:I""")
+# (id 12 stays unassigned: t2o_args_sizeof(12) is published as -1)
+QSelectArgs = _args_class("QSelectArgs", 13, """q_on:P, q_tg:P, q_ts:I, n_actions:I, actions:P, act_sb:J, act_st:J,
+    avail:P, av_sb:J, av_st:J, qmode_on:I, qmode_tg:I, qv_on:P, qv_tg:P, y_on:P, y_tg:P, B:I, T_on:I, T_tg:I, A:I""")
+QmixFwdArgs = _args_class("QmixFwdArgs", 14, """params_on:P, params_tg:P, states:P, st_sb:J, st_st:J, qv_on:P, qv_tg:P,
+    y_on:P, y_tg:P, B:I, T_on:I, T_tg:I, A:I, S:I, M:I, H:I, pos_func:I, pos_beta:F, reserved_:I""")
+QmixBwdArgs = _args_class("QmixBwdArgs", 15, """params:P, states:P, st_sb:J, st_st:J, qv:P, gy:P, gqv:P, gslabs:P,
+    work:P, work_floats:J, max_slabs:I, phase:I, B:I, T:I, A:I, S:I, M:I, H:I, pos_func:I, pos_beta:F""")
 ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs, TDQLambdaArgs,
-                NoiseArgs, NoisyFwdArgs, NoisyBwdArgs, NoisyWgradArgs)
+                NoiseArgs, NoisyFwdArgs, NoisyBwdArgs, NoisyWgradArgs, QSelectArgs, QmixFwdArgs, QmixBwdArgs)
 NOISE_KINDS = {"learner_online": 0, "learner_target": 1, "runner": 2, "module": 3}  # include/t2omca.h T2O_NOISE_*
 EP_STATS = 10  # include/t2omca.h T2O_EP_STATS
 
@@ -144,6 +151,13 @@ EXPORTS = {
     "t2o_noisy_head_bwd": (ctypes.c_int, [ctypes.POINTER(NoisyBwdArgs), ctypes.c_void_p]),
     "t2o_noisy_head_parts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "t2o_noisy_head_wgrad": (ctypes.c_int, [ctypes.POINTER(NoisyWgradArgs), ctypes.c_void_p]),
+    "t2o_q_select": (ctypes.c_int, [ctypes.POINTER(QSelectArgs), ctypes.c_void_p]),
+    "t2o_qmix_param_count": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "t2o_qmix_fwd": (ctypes.c_int, [ctypes.POINTER(QmixFwdArgs), ctypes.c_void_p]),
+    "t2o_qmix_bwd": (ctypes.c_int, [ctypes.POINTER(QmixBwdArgs), ctypes.c_void_p]),
+    "t2o_qmix_bwd_slabs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "t2o_qmix_bwd_work_floats": (ctypes.c_int64, [ctypes.c_int] * 4),
+    "t2o_vdn_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
     "t2o_probe_lane_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_scatter_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_xdl_hazards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -180,11 +194,15 @@ _DIAGNOSTIC = {"t2o_bf_swz", "t2o_probe_lane_ops", "t2o_probe_scatter_ops", "t2o
 _OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats", "t2o_td_qlambda", "t2o_rmsprop_step",
                            # ... and the NoisyNet head
                            "t2o_noise_normal", "t2o_noisy_head_fwd", "t2o_noisy_head_bwd", "t2o_noisy_head_parts",
-                           "t2o_noisy_head_wgrad"}
+                           "t2o_noisy_head_wgrad",
+                           # ... and the QMIX / VDN mixers
+                           "t2o_q_select", "t2o_qmix_param_count", "t2o_qmix_fwd", "t2o_qmix_bwd",
+                           "t2o_qmix_bwd_slabs", "t2o_qmix_bwd_work_floats", "t2o_vdn_bwd"}
 # argument structs of optional exports: no size to check where the export is absent
 _STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats", TDQLambdaArgs: "t2o_td_qlambda", NoiseArgs: "t2o_noise_normal",
                   NoisyFwdArgs: "t2o_noisy_head_fwd", NoisyBwdArgs: "t2o_noisy_head_bwd",
-                  NoisyWgradArgs: "t2o_noisy_head_wgrad"}
+                  NoisyWgradArgs: "t2o_noisy_head_wgrad", QSelectArgs: "t2o_q_select",
+                  QmixFwdArgs: "t2o_qmix_fwd", QmixBwdArgs: "t2o_qmix_bwd"}
 
 _lib = None
 

@@ -350,6 +350,9 @@ extern "C" int t2o_args_sizeof(int which) {
     case T2O_ARGS_NOISY_FWD: return (int)sizeof(t2o_noisy_fwd_args);
     case T2O_ARGS_NOISY_BWD: return (int)sizeof(t2o_noisy_bwd_args);
     case T2O_ARGS_NOISY_WGRAD: return (int)sizeof(t2o_noisy_wgrad_args);
+    case T2O_ARGS_Q_SELECT: return (int)sizeof(t2o_q_select_args);
+    case T2O_ARGS_QMIX_FWD: return (int)sizeof(t2o_qmix_fwd_args);
+    case T2O_ARGS_QMIX_BWD: return (int)sizeof(t2o_qmix_bwd_args);
     default: return -1;
   }
 }

@@ -48,6 +48,21 @@ issues none of them:
 The mixers, the TD loss and the Q(λ) taken mix read the q arrays and run unchanged.
 The head is fp32 in both precisions.  noise_seed is NOT mixed with the rank: every
 data-parallel rank draws the same network, so the shard sum is the full-batch gradient.
+
+A QMIX or VDN mixer (modules.QMixer / VDNMixer, ``mixer.kind`` "qmix" / "vdn"; DESIGN.md
+§5) replaces the two mixer steps — a TransformerMixer learner launches exactly the above:
+
+  chosen Q (t < T) and double-Q selection (t <= T),        t2o_q_select (1 launch; vdn:
+      both networks                                         its row sums are the mix)
+  qmix: both networks' mix                                  t2o_qmix_fwd (1 launch)
+  [q_lambda: the target Q at the actions, and its mix       t2o_q_select, t2o_qmix_fwd (one network)]
+  dL/dq_chosen, the rows' activations                       t2o_qmix_bwd phase 1 (vdn: t2o_vdn_bwd)
+  qmix: weight-gradient slabs, their sum into the flat      t2o_qmix_bwd phase 2, t2o_reduce_slabs: side
+      gradient, the mixer half's all-reduce                 stream, beside the agent BPTT
+These mixers read the state alone: no gradient reaches the agents' hidden states
+(detach_mixer_hidden has no effect), they are fp32 in both precisions, read their
+parameters straight from the flat buffers (no pack), and run the sequential update
+(pipeline=True is a ValueError; "auto" never pipelines them).
 """
 import dataclasses
 import os
@@ -62,6 +77,18 @@ from .state import check_fields, copy_checked
 
 
 OPTIMIZERS = {"adam": "Adam", "rmsprop": "RMSprop"}  # TDLearner(optimizer=...): the torch.optim class of opt.th
+MIXERS = ("transformer", "qmix", "vdn")  # modules.TransformerMixer / QMixer / VDNMixer .kind
+
+
+def _mixer_kind_of(state_dict):
+    """Which of MIXERS wrote this mixer.th (None: none of them), by its keys."""
+    if not state_dict:
+        return "vdn"
+    if "hyper_w1.0.weight" in state_dict:
+        return "qmix"
+    if any(k.startswith("transformer.tblocks") for k in state_dict):
+        return "transformer"
+    return None
 
 
 def _optimiser_of(opt_state):
@@ -115,6 +142,13 @@ class TDLearner:
             raise ValueError(f"optimizer must be one of {list(OPTIMIZERS)}, got {optimizer!r}")
         if not 0.0 <= float(optim_alpha) < 1.0:
             raise ValueError(f"optim_alpha must lie in [0, 1), got {optim_alpha!r}")
+        # which mixer (modules.*.kind): the reference's TransformerMixer, or the declared QMIX / VDN
+        self.mixer_kind = getattr(mixer, "kind", "transformer")
+        if self.mixer_kind not in MIXERS:
+            raise ValueError(f"mixer.kind must be one of {list(MIXERS)}, got {self.mixer_kind!r}")
+        if pipeline is True and self.mixer_kind != "transformer":
+            raise ValueError(f"pipeline=True runs the update in step ranges, which needs the decoupled transformer "
+                             f"mixer; a {self.mixer_kind} mixer runs the sequential update (pipeline='auto' or False)")
         dev = next(agent.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("TDLearner needs the modules on a HIP device (no CPU fallback)")
@@ -125,12 +159,15 @@ class TDLearner:
         prec = 1 if precision == "bf16" else 0
         self.precision = precision
         self.sa = dataclasses.replace(agent.shape, prec=prec)
-        self.sm = dataclasses.replace(mixer.shape, prec=prec)
+        if self.mixer_kind == "transformer":
+            self.sm = dataclasses.replace(mixer.shape, prec=prec)
+        else:  # ops.QmixShape (fp32 in both precisions), or None: VDN has no parameters
+            self.sm = getattr(mixer, "shape", None)
         # a noisy agent's flat parameters: the plain agent's na_net floats (what the packs and
         # the fused kernels read), then the head's NA·(E+1) sigmas
         self.noisy = bool(getattr(agent, "noisy", False))
         self.noise_seed = int(noise_seed)
-        self.na_net, self.nm = self.sa.n_params, self.sm.n_params
+        self.na_net, self.nm = self.sa.n_params, self.sm.n_params if self.sm is not None else 0
         self.n_head = self.sa.NA * (self.sa.E + 1)
         self.na = self.na_net + (self.n_head if self.noisy else 0)
         assert self.na == sum(p.numel() for p in agent.parameters())
@@ -175,9 +212,10 @@ class TDLearner:
         self.last_target_update_episode = 0
         self.timer = None   # optional callable(tag) recording HIP events around the big kernels
         self.pack_a = torch.empty(self.sa.layout().pack_floats, device=dev)
-        self.pack_m = torch.empty(self.sm.layout().pack_floats, device=dev)
         self.pack_at = torch.empty_like(self.pack_a)
-        self.pack_mt = torch.empty_like(self.pack_m)
+        if self.mixer_kind == "transformer":  # (the other mixers read the flat parameters: no pack)
+            self.pack_m = torch.empty(self.sm.layout().pack_floats, device=dev)
+            self.pack_mt = torch.empty_like(self.pack_m)
         self._pack_targets()
         self._slabs = {}
         # logged statistics (PyMARL2 NQLearner: every learner_log_interval env steps);
@@ -229,7 +267,8 @@ class TDLearner:
 
     def _pack_targets(self):
         ops.pack_params(self.sa, self.target_params[:self.na_net], self.pack_at)
-        ops.pack_params(self.sm, self.target_params[self.na:], self.pack_mt)
+        if self.mixer_kind == "transformer":
+            ops.pack_params(self.sm, self.target_params[self.na:], self.pack_mt)
 
     def update_targets(self):
         self.target_params.copy_(self.params)
@@ -303,7 +342,9 @@ class TDLearner:
         """Inverse of save_models; also takes checkpoints written by the reference
         framework.  As PyMARL2's NQLearner does, the target agent is reloaded from
         agent.th and the target mixer is left as it is; opt.th is optional, and one
-        written by the other optimiser is a ValueError naming both.  opt.th follows the
+        written by the other optimiser is a ValueError naming both, and so is a mixer.th
+        of another kind of mixer (told by its keys: transformer, qmix, or vdn's empty
+        dict).  opt.th follows the
         modules' parameter order (a noisy agent: q_basic.u_w, u_b, s_w, s_b last of the
         agent's); an agent.th of the other head, or an opt.th whose per-parameter shapes
         are not these modules', is a ValueError that says so.  Every check comes before
@@ -320,6 +361,10 @@ class TDLearner:
             kinds = ("a NoisyLinear (noisy-new)", "a plain Linear")
             raise ValueError(f"agent.th holds {kinds['q_basic.u_w' not in agent_sd]} q_basic head, this learner's "
                              f"agent has {kinds[self.noisy]} one (noisy={self.noisy})")
+        mixer_sd = load("mixer.th")
+        if _mixer_kind_of(mixer_sd) != self.mixer_kind:
+            raise ValueError(f"mixer.th holds a {_mixer_kind_of(mixer_sd)} mixer, this learner's mixer is a "
+                             f"{self.mixer_kind} one")
         if saved is not None:
             params = list(self.agent.parameters()) + list(self.mixer.parameters())
             ids = [i for g in saved.get("param_groups", []) for i in g["params"]]
@@ -335,7 +380,7 @@ class TDLearner:
                                          f"do not match these modules' parameter order")
         with torch.no_grad():
             self.agent.load_state_dict(agent_sd)  # copies into the flat-buffer views
-            self.mixer.load_state_dict(load("mixer.th"))
+            self.mixer.load_state_dict(mixer_sd)
             self.target_params[:self.na].copy_(self.params[:self.na])
         if saved is None:
             self._sync_replicas()
@@ -375,7 +420,9 @@ class TDLearner:
                 "optim_alpha": torch.tensor(self.alpha, dtype=torch.float64),
                 # the NoisyNet head: with it `na` covers the sigmas; its noise is a function of
                 # noise_seed and step_count alone, so no further state
-                "noisy": self.noisy, "noise_seed": self.noise_seed}
+                "noisy": self.noisy, "noise_seed": self.noise_seed,
+                # the kind of mixer (MIXERS) the mixer half of the flat buffers belongs to
+                "mixer": self.mixer_kind}
 
     def load_state_dict(self, sd):
         """In place into the flat buffers, which the modules' parameters view; then
@@ -384,12 +431,14 @@ class TDLearner:
         naming the field when the parameter counts, the precision, the targets
         (q_lambda) or the optimiser differ; a state saved before the last three
         existed holds their defaults.  Likewise `noisy` (a state saved before it
-        existed is a plain agent's), and with a noisy agent `noise_seed`."""
-        sd = {"q_lambda": False, "optimizer": "adam", "optim_alpha": 0.99, "noisy": False, "noise_seed": 0, **sd}
+        existed is a plain agent's), and with a noisy agent `noise_seed`; and `mixer`, the
+        kind of mixer (a state saved before it existed is a transformer mixer's)."""
+        sd = {"q_lambda": False, "optimizer": "adam", "optim_alpha": 0.99, "noisy": False, "noise_seed": 0,
+              "mixer": "transformer", **sd}
         sd["optim_alpha"] = float(sd["optim_alpha"])
         # (noisy before na: a noisy state in a plain learner is told by its name, not by its size)
         head = {"noisy": self.noisy, **({"noise_seed": self.noise_seed} if self.noisy else {})}
-        check_fields("TDLearner", sd, {"format": 1, **head, "na": self.na, "nm": self.nm, "precision": self.precision,
+        check_fields("TDLearner", sd, {"format": 1, "mixer": self.mixer_kind, **head, "na": self.na, "nm": self.nm, "precision": self.precision,
                                        "q_lambda": self.q_lambda, "optimizer": self.optimizer,
                                        "optim_alpha": self.alpha})
         with torch.no_grad():
@@ -415,6 +464,8 @@ class TDLearner:
         """Run the update's recurrences in step ranges on two streams?  Only where the
         mixer runs decoupled (a multi-tile mixer at a small batch, t2o_mixer_split)
         and the agent BPTT is the pipelined kernel (depth 2), which take ranges."""
+        if self.mixer_kind != "transformer":
+            return False  # (the QMIX / VDN mixers run the sequential update)
         if self.pipeline is False or self.contract == "pair" or self.sa.D != 2 or self.sa.generic or self.sm.generic:
             return False
         lib = ops.lib()
@@ -459,6 +510,8 @@ class TDLearner:
             w = torch.as_tensor(np.asarray(per_weight) if not torch.is_tensor(per_weight) else per_weight,
                                 dtype=torch.float32).to(dev).reshape(B).contiguous()
 
+        if self.mixer_kind != "transformer":
+            return self._train_flat_mixer(obs, state, act, avail, reward, term, filled, w, t_env, episode_num)
         # the gradient buffer is cleared on the side stream, off the critical path
         # (after the previous update's Adam, which read it)
         main = torch.cuda.current_stream(dev)
@@ -631,6 +684,102 @@ class TDLearner:
             wait_all((work_m, work_a))
         return self._finish(episode_num, td, o_on, t_env, term, filled)
 
+    def _train_flat_mixer(self, obs, state, act, avail, reward, term, filled, w, t_env, episode_num):
+        """train() with a QMIX or VDN mixer (module docstring): the agent unroll, the TD
+        loss, the agent BPTT, the optimiser step and the statistics are the transformer
+        path's; steps 2 and 4 are the select kernel and the flat mixers' kernels.  The
+        mixers read the state alone, so gh is None: no gradient reaches the agents'
+        hidden states from them and detach_mixer_hidden has no effect."""
+        B, T1, A, _ = obs.shape
+        T = T1 - 1
+        dev = self.device
+        vdn = self.mixer_kind == "vdn"
+        state = state.reshape(B, T1, -1) if state.dim() != 3 else state
+        p_on, p_tg = self.params[self.na:], self.target_params[self.na:]
+        main = torch.cuda.current_stream(dev)
+        side = self._side_stream() if self.overlap else main
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            if self.noisy:
+                eps_on, eps_tg = self._draw_noise(T1)
+                noise_drawn = side.record_event()
+            self.grad.zero_()
+            grad_clear = side.record_event()
+        ops.pack_params(self.sa, self.params[:self.na_net], self.pack_a)
+        hmid = self._buf("hmid", (B, T1, self.sa.D - 1, A, self.sa.E)) if self.sa.D > 1 else None
+        # 1. agents: online + target over t = 0..T
+        q_on, h_on, q_tg, h_tg = ops.agent_unroll_fwd(self.sa, self.pack_a, obs, pack_tg=self.pack_at,
+                                                      timer=self.timer, hmid_on=hmid)
+        if self.noisy:
+            main.wait_event(noise_drawn)
+            self._head_fwd(q_on, h_on, q_tg, h_tg, eps_on, eps_tg)
+        # 2. chosen Q (t < T) and double-Q selection (t <= T); VDN's mix is the kernel's row sum
+        qv_on, qv_tg = self._buf("qv_on", (B, T, A)), self._buf("qv_tg", (B, T1, A))
+        y_on, y_tg = torch.empty(B, T, device=dev), torch.empty(B, T1, device=dev)
+        ops.q_select(q_on, qmode_on=1, actions=act, avail=avail, T_on=T, q_tg=q_tg, qmode_tg=2, T_tg=T1,
+                     outs=((qv_on, y_on if vdn else None), (qv_tg, y_tg if vdn else None)), timer=self.timer)
+        if not vdn:
+            ops.qmix_fwd(self.sm, p_on, state, qv_on, params_tg=p_tg, qv_tg=qv_tg, outs=(y_on, y_tg), timer=self.timer)
+        self.last_qv = (qv_on, qv_tg)  # what the mixers read (buffers the next update reuses)
+        if self.q_lambda:  # the target mixer on the target Q at the batch's actions, t < T
+            qv_tk, y_tk = self._buf("qv_tk", (B, T, A)), torch.empty(B, T, device=dev)
+            ops.q_select(q_tg, qmode_on=1, actions=act, T_on=T, outs=(qv_tk, y_tk if vdn else None), timer=self.timer)
+            if not vdn:
+                ops.qmix_fwd(self.sm, p_tg, state, qv_tk, outs=y_tk, timer=self.timer)
+        # 3. TD(λ) / Q(λ) targets and the loss (Σ mask lands in grad[-1], cleared on the side stream)
+        main.wait_event(grad_clear)
+        td_kw = dict(gamma=self.gamma, td_lambda=self.td_lambda, mask_sum=1.0, algo=self.td_algo,
+                     mask_sum_acc=self.grad[-1:])
+        if self.q_lambda:
+            td = ops.td_qlambda(y_on, y_tg, y_tk, reward, term, filled, w, **td_kw)
+            td["qtot_taken"], td["qtot_tgt"] = y_tk, y_tg
+        else:
+            td = ops.td_loss(y_on, y_tg, reward, term, filled, w, **td_kw)
+        # 4. the mixer's backward: dL/dq_chosen now, its weight gradients beside the agent BPTT
+        gqv = self._buf("gqv", (B, T, A))
+        mixer_dw = None
+        if vdn:
+            ops.vdn_bwd(td["gq"], gqv=gqv, timer=self.timer)
+        else:
+            slabs = self._slab("qmix", ops.qmix_slab_count(B, T) * self.nm)
+            work = self._slab("qmix_work", ops.qmix_work_floats(self.sm, B, T))
+            mixer_dw, _, _, nslab = ops.qmix_bwd(self.sm, p_on, state, qv_on, td["gq"], gqv=gqv, slabs=slabs,
+                                                 work=work, timer=self.timer, launcher=True)
+            mixer_dw(1)
+        gh, gchosen = None, gqv
+        if self.noisy:  # dL/dh = dL/dq_chosen · W_t[action]; the agent BPTT then takes no q gradient
+            gh, gpart = self._head_bwd(gqv, act, h_on, eps_on, None)
+            gchosen = None
+        tape_a = self._slab("tape_a", ops.tape_floats(self.sa, ops.agent_tape_tiles(B, T, A)))
+        slabs_a = self._slab("a", ops.agent_slab_count(B, A) * self.sa.layout().grad_total)
+
+        def mixer_grads():
+            if mixer_dw is not None:
+                mixer_dw(2)
+                ops.reduce_slabs(slabs, nslab, self.grad[self.na:self.na + self.nm])
+
+        def agent_grads():
+            # 5. agent BPTT, its gradients in the reference parameter order
+            ga, _ = ops.agent_unroll_bwd(self.sa, self.pack_a, obs, h_on, gchosen=gchosen, actions=act, gh=gh,
+                                         slabs=slabs_a, timer=self.timer, hmid=hmid, tape=tape_a)
+            ops.unpack_grads(self.sa, self.params[:self.na_net], ga, self.grad[:self.na_net])
+            if self.noisy:
+                self._head_wgrad(gpart, B, A, eps_on)
+        if self.contract == "pair":  # everything on this stream, one all-reduce
+            agent_grads()
+            mixer_grads()
+            wait_all((allreduce_async(self.grad, self.pg),))
+        else:
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                mixer_grads()
+                work_m = allreduce_async(self.grad[self.na:], self.pg)  # (vdn: Σ mask alone)
+            agent_grads()
+            work_a = allreduce_async(self.grad[:self.na], self.pg)
+            main.wait_stream(side)
+            wait_all((work_m, work_a))
+        return self._finish(episode_num, td, {"y": y_on}, t_env, term, filled)
+
     def _taken_mix(self, state, h_tg, q_tg, act, B, T):
         """q_lambda: the target mixer once more, on the target Q at the batch's actions
         (t < T; qmode 1 from q_tg, the target agents' hidden states) — a one-network
@@ -687,7 +836,8 @@ class TDLearner:
         if self._world() > 1:
             dist.all_reduce(st, op=dist.ReduceOp.SUM, group=self.pg)
         loss_sum, mask_sum, m, abs_sum, q_sum, tgt_sum, grad_norm = torch.cat([st, self.grad_norm.double()]).tolist()
-        n_agents = self.sm.agents
+        # (the mixer kind's own field: the transformer / QMIX shape's agents, VDN's from the agent network)
+        n_agents = self.sm.agents if self.sm is not None else self.agent.n_agents
         log = self.logger.log_stat
         log("loss_td", loss_sum / mask_sum, t_env)
         log("grad_norm", grad_norm, t_env)

@@ -296,6 +296,8 @@ class TransformerMixer(nn.Module):
     feature width), n_entities_state != n_agents and use_orthogonal (:48-50).
     Shapes without a tuned MFMA instance run the runtime-shaped kernels."""
 
+    kind = "transformer"
+
     def __init__(self, args, abs=True):
         super().__init__()
         self.args = args
@@ -331,3 +333,116 @@ class TransformerMixer(nn.Module):
         tokens = states if self.custom_space else obs  # n_transf_mixer.py:60-63
         params, flat, pack = self._pack_cache.get(self, self.shape)
         return _MixerStep.apply(self.shape, flat, pack, qvals, hidden_states, hyper_weights, tokens, *params)
+
+
+class _QMixStep(torch.autograd.Function):
+    """QMixer.forward on the HIP kernels (t2o_qmix_fwd / t2o_qmix_bwd): the parameters
+    enter as separate inputs, their gradients leave as views of one flat buffer (the
+    slab sum, in the parameter order)."""
+
+    @staticmethod
+    def forward(ctx, shape, qvals, states, *params):
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1) for p in params])
+        qv = qvals.detach().contiguous()
+        st = states.detach()
+        if st.stride(2) != 1:
+            st = st.contiguous()
+        y = ops.qmix_fwd(shape, flat, st, qv)
+        ctx.save_for_backward(flat, qv, st)
+        ctx.shape, ctx.param_shapes = shape, [p.shape for p in params]
+        return y.unsqueeze(2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        flat, qv, st = ctx.saved_tensors
+        gqv, slabs, nslab = ops.qmix_bwd(ctx.shape, flat, st, qv, gy.reshape(qv.shape[:2]).contiguous())
+        gflat = ops.reduce_slabs(slabs, nslab, torch.empty_like(flat))
+        return (None, gqv, None) + _split_like(gflat, ctx.param_shapes)
+
+
+class QMixer(nn.Module):
+    """The classic QMIX hypernetwork mixer, PyMARL2's modules/mixers/nmix.py `Mixer`.
+    It does not ship with the reference (n_transf_mixer.py only): this is the DECLARED
+    definition of DESIGN.md §5, parity-unpinned.  Per (episode, step) row
+
+        w1 = pos(hyper_w1(s)).view(A, M)    b1 = hyper_b1(s)
+        w2 = pos(hyper_w2(s))               b2 = hyper_b2(s)
+        y  = elu(q @ w1 + b1) @ w2 + b2
+
+    with M = args.mixing_embed_dim (32), H = args.hypernet_embed (64), the state width
+    S = prod(args.state_shape) (default: the state's entities x state_entity_feats) and
+    pos the qmix_pos_func of TransformerMixer (``abs=False``: identity).  Torch's
+    default initialisation.  What the kernels do not take is a ValueError here."""
+
+    kind = "qmix"
+
+    def __init__(self, args, abs=True):
+        super().__init__()
+        self.args = args
+        self.n_agents = A = int(args.n_agents)
+        self.embed_dim = M = int(getattr(args, "mixing_embed_dim", 32))
+        self.hypernet_embed = H = int(getattr(args, "hypernet_embed", 64))
+        state_shape = getattr(args, "state_shape", None)
+        if state_shape is None:
+            state_shape = getattr(args, "n_entities_state", args.n_entities) * args.state_entity_feats
+        self.state_dim = S = int(torch.Size([state_shape] if isinstance(state_shape, int) else state_shape).numel())
+        self.qmix_pos_func = getattr(args, "qmix_pos_func", "abs") if abs else "identity"
+        if not (1 <= A <= 64 and 1 <= S <= 1024 and M in (16, 32) and H in (32, 64)):
+            raise ValueError(f"QMixer: n_agents={A}, state width {S}, mixing_embed_dim={M}, hypernet_embed={H}: the "
+                             f"QMIX kernels take {ops.QMIX_LIMITS}")
+        self.hyper_w1 = nn.Sequential(nn.Linear(S, H), nn.ReLU(inplace=True), nn.Linear(H, A * M))
+        self.hyper_b1 = nn.Sequential(nn.Linear(S, M))
+        self.hyper_w2 = nn.Sequential(nn.Linear(S, H), nn.ReLU(inplace=True), nn.Linear(H, M))
+        self.hyper_b2 = nn.Sequential(nn.Linear(S, M), nn.ReLU(inplace=True), nn.Linear(M, 1))
+        pos = _lib.POS_FUNCS.get(self.qmix_pos_func, 3)
+        beta = float(getattr(args, "qmix_pos_func_beta", 1.0)) if self.qmix_pos_func == "softplus" else 1.0
+        self.shape = ops.QmixShape(A, S, M, H, pos_func=pos, pos_beta=beta)
+        # the learner reads the state whatever state_entity_mode says (these mixers take no obs tokens)
+        self.custom_space = True
+
+    def forward(self, qvals, states):
+        if not qvals.is_cuda:
+            raise RuntimeError("QMixer.forward needs HIP-device tensors (no CPU fallback)")
+        b, T = qvals.shape[:2]
+        return _QMixStep.apply(self.shape, qvals.reshape(b, T, self.n_agents), states.reshape(b, T, self.state_dim),
+                               *self.parameters())
+
+
+class _VDNStep(torch.autograd.Function):
+    """VDNMixer.forward on the HIP kernels: the row sum of the select kernel's family
+    (t2o_vdn_bwd spreads the gradient back)."""
+
+    @staticmethod
+    def forward(ctx, qvals):
+        qv = qvals.detach().contiguous()
+        ctx.A = qv.shape[2]
+        return ops.vdn_fwd(qv).unsqueeze(2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return ops.vdn_bwd(gy[..., 0].contiguous(), A=ctx.A)
+
+
+class VDNMixer(nn.Module):
+    """PyMARL2's modules/mixers/vdn.py: y = Σ_a q_a.  No parameters.  (Declared, absent
+    from the reference: DESIGN.md §5.)"""
+
+    kind = "vdn"
+    custom_space = True
+
+    def forward(self, qvals, states=None):
+        if not qvals.is_cuda:
+            raise RuntimeError("VDNMixer.forward needs HIP-device tensors (no CPU fallback)")
+        return _VDNStep.apply(qvals)
+
+
+def make_mixer(args):
+    """args.mixer: "qmix" -> QMixer, "vdn" -> VDNMixer, absent or anything else ->
+    the reference's TransformerMixer."""
+    name = getattr(args, "mixer", None)
+    if name == "qmix":
+        return QMixer(args)
+    if name == "vdn":
+        return VDNMixer()
+    return TransformerMixer(args)

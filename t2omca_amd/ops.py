@@ -806,3 +806,219 @@ def episode_stats(reward, info, terminated, returns, acc):
     check(lib().t2o_episode_stats(ptr(reward), ptr(info), ptr(terminated), ptr(returns), n, ptr(acc),
                                   stream_ptr(acc.device)), "episode_stats")
     return acc
+
+
+# ---- the QMIX and VDN mixers (include/t2omca.h t2o_q_select / t2o_qmix_* / t2o_vdn_bwd) ----
+
+@dataclass(frozen=True)
+class QmixShape:
+    """Sizes of a QMixer (modules.QMixer): agents, state width, mixing_embed_dim M,
+    hypernet_embed H, and the positivity function of the hypernetwork weights."""
+    A: int
+    S: int
+    M: int = 32
+    H: int = 64
+    pos_func: int = 0
+    pos_beta: float = 1.0
+
+    @property
+    def n_params(self):
+        return int(lib().t2o_qmix_param_count(self.A, self.S, self.M, self.H))
+
+    @property
+    def agents(self):
+        return self.A
+
+
+QMIX_LIMITS = "1 <= n_agents <= 64, 1 <= state width <= 1024, mixing_embed_dim in {16, 32}, hypernet_embed in {32, 64}"
+
+
+def qmix_param_blocks(A, S, M=32, H=64):
+    """(state_dict key, shape) of a QMixer's parameters in their flat order."""
+    return [("hyper_w1.0.weight", (H, S)), ("hyper_w1.0.bias", (H,)), ("hyper_w1.2.weight", (A * M, H)),
+            ("hyper_w1.2.bias", (A * M,)), ("hyper_b1.0.weight", (M, S)), ("hyper_b1.0.bias", (M,)),
+            ("hyper_w2.0.weight", (H, S)), ("hyper_w2.0.bias", (H,)), ("hyper_w2.2.weight", (M, H)),
+            ("hyper_w2.2.bias", (M,)), ("hyper_b2.0.weight", (M, S)), ("hyper_b2.0.bias", (M,)),
+            ("hyper_b2.2.weight", (1, M)), ("hyper_b2.2.bias", (1,))]
+
+
+def _i64c(name, t):
+    if not t.is_cuda:
+        raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    if t.dtype != torch.int64 or t.dim() != 3 or t.stride(2) != 1:
+        raise TypeError(f"{name}: expected an int64 tensor [B, >= T, A] with unit agent stride")
+    return t
+
+
+def q_select(q_on, *, qmode_on=1, actions=None, avail=None, T_on=None, q_tg=None, qmode_tg=2, T_tg=None,
+             want_y=False, outs=None, timer=None):
+    """The learner's chosen-Q gather / double-Q selection (t2o_q_select).  q_on / q_tg
+    [B, q_ts, A, NA] dense float32; actions int64 [B, >= T, A] (any episode / step
+    strides); avail int32 [B, >= T, A, NA] or None.  qmode 1: the network's Q at the
+    actions; 2: at the argmax of q_on masked by avail (ties: the lowest index).  The
+    first network covers t < T_on, the second (q_tg given) t < T_tg.  Returns
+    (qv_on, y_on) or ((qv_on, y_on), (qv_tg, y_tg)); y = Σ_a qv when want_y, else None.
+    outs: the same structure of preallocated dense tensors."""
+    _f32c("q_select: q_on", q_on)
+    B, q_ts, A, NA = q_on.shape
+    T_on = int(T_on or q_ts)
+    two = q_tg is not None
+    if two:
+        _f32c("q_select: q_tg", q_tg, (B, q_ts, A, NA))
+        T_tg = int(T_tg or q_ts)
+    if qmode_on not in (1, 2) or (two and qmode_tg not in (1, 2)):
+        raise ValueError("q_select: qmode must be 1 (gather at the actions) or 2 (double-Q argmax)")
+    if actions is not None:
+        _i64c("q_select: actions", actions)
+    elif qmode_on == 1 or (two and qmode_tg == 1):
+        raise ValueError("q_select: qmode 1 needs the actions")
+    if avail is not None:
+        if not avail.is_cuda:
+            raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+        if avail.dtype != torch.int32 or avail.stride(3) != 1 or avail.stride(2) != NA:
+            raise TypeError("q_select: avail must be int32 [B, >= T, A, NA] with dense [A, NA] rows")
+    dev = q_on.device
+
+    def alloc(T):
+        return (torch.empty(B, T, A, device=dev), torch.empty(B, T, device=dev) if want_y else None)
+    if outs is None:
+        outs = (alloc(T_on), alloc(T_tg)) if two else alloc(T_on)
+    (qv_on, y_on), (qv_tg, y_tg) = (outs if two else (outs, (None, None)))
+    _f32c("q_select: qv_on", qv_on, (B, T_on, A))
+    if y_on is not None:
+        _f32c("q_select: y_on", y_on, (B, T_on))
+    if two:
+        _f32c("q_select: qv_tg", qv_tg, (B, T_tg, A))
+        if y_tg is not None:
+            _f32c("q_select: y_tg", y_tg, (B, T_tg))
+    act_sb, act_st = _mstrides(actions)
+    av_sb, av_st = _mstrides(avail)
+    a = _lib.QSelectArgs(q_on=_p(q_on), q_tg=_p(q_tg), q_ts=q_ts, n_actions=NA, actions=_p(actions), act_sb=act_sb,
+                         act_st=act_st, avail=_p(avail), av_sb=av_sb, av_st=av_st, qmode_on=qmode_on,
+                         qmode_tg=qmode_tg if two else 0, qv_on=_p(qv_on), qv_tg=_p(qv_tg), y_on=_p(y_on),
+                         y_tg=_p(y_tg), B=B, T_on=T_on, T_tg=T_tg if two else 0, A=A)
+    _mark(timer, "begin:q_select")
+    check(lib().t2o_q_select(ctypes.byref(a), stream_ptr(dev)), "q_select")
+    _mark(timer, "end:q_select")
+    return outs
+
+
+def _qmix_states(name, states, B, S):
+    if not states.is_cuda:
+        raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    if states.dtype != torch.float32 or states.dim() != 3 or states.shape[0] != B or states.shape[2] != S or \
+            states.stride(2) != 1:
+        raise TypeError(f"{name}: states must be float32 [B, >= T, {S}] with unit feature stride")
+    return states
+
+
+def qmix_fwd(shape: QmixShape, params_on, states, qv_on, *, params_tg=None, qv_tg=None, outs=None, timer=None):
+    """QMIX forward (t2o_qmix_fwd) of one or two networks in one launch.  params_*:
+    the mixer's flat parameters (dense float32, shape.n_params); states [B, >= T, S]
+    (any episode / step strides); qv_* [B, T_*, A] dense.  Returns y_on [B, T_on], or
+    (y_on, y_tg)."""
+    B, T_on, A = qv_on.shape
+    _f32c("qmix_fwd: params_on", params_on, (shape.n_params,))
+    _f32c("qmix_fwd: qv_on", qv_on, (B, T_on, shape.A))
+    _qmix_states("qmix_fwd", states, B, shape.S)
+    two = params_tg is not None
+    T_tg = 0
+    if two:
+        T_tg = qv_tg.shape[1]
+        _f32c("qmix_fwd: params_tg", params_tg, (shape.n_params,))
+        _f32c("qmix_fwd: qv_tg", qv_tg, (B, T_tg, shape.A))
+    if states.shape[1] < max(T_on, T_tg):
+        raise ValueError(f"qmix_fwd: {max(T_on, T_tg)} steps, the states cover {states.shape[1]}")
+    dev = qv_on.device
+    if outs is None:
+        outs = (torch.empty(B, T_on, device=dev), torch.empty(B, T_tg, device=dev)) if two else \
+            torch.empty(B, T_on, device=dev)
+    y_on, y_tg = outs if two else (outs, None)
+    _f32c("qmix_fwd: y_on", y_on, (B, T_on))
+    if two:
+        _f32c("qmix_fwd: y_tg", y_tg, (B, T_tg))
+    a = _lib.QmixFwdArgs(params_on=_p(params_on), params_tg=_p(params_tg), states=_p(states), st_sb=states.stride(0),
+                         st_st=states.stride(1), qv_on=_p(qv_on), qv_tg=_p(qv_tg), y_on=_p(y_on), y_tg=_p(y_tg),
+                         B=B, T_on=T_on, T_tg=T_tg, A=shape.A, S=shape.S, M=shape.M, H=shape.H,
+                         pos_func=shape.pos_func, pos_beta=float(shape.pos_beta))
+    _mark(timer, "begin:qmix_fwd")
+    check(lib().t2o_qmix_fwd(ctypes.byref(a), stream_ptr(dev)), "qmix_fwd")
+    _mark(timer, "end:qmix_fwd")
+    return outs
+
+
+def qmix_slab_count(B, T):
+    n = int(lib().t2o_qmix_bwd_slabs(int(B), int(T)))
+    if n < 1:
+        raise ValueError(f"qmix_slab_count: bad shape B={B} T={T}")
+    return n
+
+
+def qmix_work_floats(shape: QmixShape, B, T):
+    n = int(lib().t2o_qmix_bwd_work_floats(int(B), int(T), shape.M, shape.H))
+    if n < 1:
+        raise ValueError(f"qmix_work_floats: bad shape B={B} T={T} M={shape.M} H={shape.H}")
+    return n
+
+
+def qmix_bwd(shape: QmixShape, params, states, qv, gy, *, gqv=None, slabs=None, work=None, timer=None,
+             launcher=False):
+    """QMIX backward (t2o_qmix_bwd) of one network: dL/dqv [B, T, A] and the partial
+    weight-gradient slabs [qmix_slab_count(B, T), n_params] (sum them with
+    reduce_slabs).  Returns (gqv, slabs, nslab); launcher: (go, gqv, slabs, nslab) with
+    go(phase) — 1 the rows (gqv and the work buffer), 2 the weight gradients."""
+    B, T, A = qv.shape
+    _f32c("qmix_bwd: params", params, (shape.n_params,))
+    _f32c("qmix_bwd: qv", qv, (B, T, shape.A))
+    _f32c("qmix_bwd: gy", gy, (B, T))
+    _qmix_states("qmix_bwd", states, B, shape.S)
+    if states.shape[1] < T:
+        raise ValueError(f"qmix_bwd: {T} steps, the states cover {states.shape[1]}")
+    dev = qv.device
+    nslab, nwork = qmix_slab_count(B, T), qmix_work_floats(shape, B, T)
+    if gqv is None:
+        gqv = torch.empty(B, T, A, device=dev)
+    if slabs is None:
+        slabs = torch.empty(nslab * shape.n_params, device=dev)
+    if work is None:
+        work = torch.empty(nwork, device=dev)
+    _f32c("qmix_bwd: gqv", gqv, (B, T, A))
+    _f32c("qmix_bwd: slabs", slabs)
+    _f32c("qmix_bwd: work", work)
+    if slabs.numel() < nslab * shape.n_params or work.numel() < nwork:
+        raise ValueError("qmix_bwd: the slab or work buffer is too small")
+    a = _lib.QmixBwdArgs(params=_p(params), states=_p(states), st_sb=states.stride(0), st_st=states.stride(1),
+                         qv=_p(qv), gy=_p(gy), gqv=_p(gqv), gslabs=_p(slabs), work=_p(work), work_floats=work.numel(),
+                         max_slabs=slabs.numel() // shape.n_params, B=B, T=T, A=shape.A, S=shape.S, M=shape.M,
+                         H=shape.H, pos_func=shape.pos_func, pos_beta=float(shape.pos_beta))
+    fn = lib().t2o_qmix_bwd
+
+    def go(phase=0):
+        a.phase = int(phase)
+        _mark(timer, "begin:qmix_bwd")
+        check(fn(ctypes.byref(a), stream_ptr(dev)), "qmix_bwd")
+        _mark(timer, "end:qmix_bwd")
+    if launcher:
+        return go, gqv, slabs, nslab
+    go(0)
+    return gqv, slabs, nslab
+
+
+def vdn_fwd(qv, timer=None):
+    """VDN forward y [B, T] = Σ_a qv[B, T, A], in agent order: the select kernel's row
+    sum (qv as a one-action Q array, whose argmax is that action)."""
+    _f32c("vdn_fwd: qv", qv)
+    return q_select(qv.unsqueeze(3), qmode_on=2, want_y=True, timer=timer)[1]
+
+
+def vdn_bwd(gy, gqv=None, A=None, timer=None):
+    """VDN backward (t2o_vdn_bwd): gqv[b, t, a] = gy[b, t]."""
+    _f32c("vdn_bwd: gy", gy)
+    B, T = gy.shape
+    if gqv is None:
+        gqv = torch.empty(B, T, int(A), device=gy.device)
+    _f32c("vdn_bwd: gqv", gqv, (B, T, gqv.shape[2]))
+    _mark(timer, "begin:vdn_bwd")
+    check(lib().t2o_vdn_bwd(_p(gy), _p(gqv), B, T, gqv.shape[2], stream_ptr(gy.device)), "vdn_bwd")
+    _mark(timer, "end:vdn_bwd")
+    return gqv
