@@ -24,6 +24,7 @@
  *   t2o_rmsprop_step       the RMSprop optimiser step (optimizer != 'adam')
  *   t2o_noise_normal / t2o_noisy_head_*  the NoisyLinear Q head (action_selector: noisy-new)
  *   t2o_q_select / t2o_qmix_* / t2o_vdn_bwd  the QMIX and VDN mixers (mixer: qmix, vdn)
+ *   t2o_qplex_*            the QPLEX duelling mixer (mixer: dmaq)
  *   t2o_env_step / reset   MultiAgvOffloadingEnv.step/reset/get_obs/get_state
  *                          (environment_multi_mec.py:184-366, normalization.py)
  *
@@ -202,6 +203,10 @@ int t2o_unpack_grads(const t2o_layout* L, const float* params, const float* gpac
 #define T2O_ARGS_Q_SELECT 13
 #define T2O_ARGS_QMIX_FWD 14
 #define T2O_ARGS_QMIX_BWD 15
+/* (16 stays unassigned too: published as unknown while 15 was the last id) */
+#define T2O_ARGS_QPLEX_SELECT 17
+#define T2O_ARGS_QPLEX_FWD 18
+#define T2O_ARGS_QPLEX_BWD 19
 int t2o_args_sizeof(int which); /* sizeof the T2O_ARGS_* struct, -1 for an unknown one */
 
 /* Agent unroll forward (TransformerAgent.forward over t, transf_agent.py:54-76) for
@@ -720,6 +725,97 @@ int64_t t2o_qmix_bwd_work_floats(int B, int T, int M, int H);
 
 /* VDN backward: gqv[b][t][a] = gy[b][t]. */
 int t2o_vdn_bwd(const float* gy, float* gqv, int B, int T, int A, void* stream);
+
+/* ---- the QPLEX duelling mixer (t2o_qplex.hip; TDLearner with mixer: dmaq / qplex).
+ * It does not ship with the reference: the DECLARED definition after PyMARL2's
+ * modules/mixers/dmaq_general.py, dmaq_si_weight.py and dmaq_qatten_learner.py at
+ * qplex.yaml's defaults (weighted_head, is_minus_one, adv_hypernet_layers 2;
+ * parity-unpinned).  Per (episode, step) row, with state s [S], the
+ * agents' q [A], their maxima m [A] and the joint action u [A] (sg: stop-gradient):
+ *   w   = |hyper_w_final(s)| + 1e-10        v = V(s)
+ *   d   = [s ; onehot(u_0) ; ... ; onehot(u_{A-1})]
+ *   κ_k = |key_k(s)| + 1e-10    α_k = sigmoid(agents_k(s))    β_k = sigmoid(action_k(d))
+ *   λ   = Σ_k κ_k α_k ⊙ β_k
+ *   y_v = Σ_a (w_a q_a + v_a)      y_adv = Σ_a sg[w_a (q_a − m_a)] (λ_a − 1)
+ * Every network is Linear(in, Hx), ReLU, Linear(Hx, out), read straight from a flat
+ * buffer in the registration order hyper_w_final, V (Hx = H, out = A), then
+ * key_extractors[0..K-1] (Hx = HA, out 1), agents_extractors[0..K-1] (out A),
+ * action_extractors[0..K-1] (in = S + A·NA, out A): t2o_qplex_param_count floats.  All
+ * arithmetic is fp32.  Limits: 1 <= A <= 64, 1 <= S <= 1024, 1 <= NA <= 16, H and HA in
+ * {32, 64}, 1 <= K <= 10, B·T < 2^27.  (Added within ABI 6: nothing existing moved.)
+ * T2O_EINVAL for a null required pointer or a bad size, before any launch; no
+ * allocation, no synchronisation, no atomics. */
+int64_t t2o_qplex_param_count(int A, int S, int NA, int H, int HA, int K);
+
+/* t2o_q_select's selection (same qmode meanings, strides and tie rule) that also
+ * writes, per (b, t, a), the avail-masked maximum of the network's OWN Q (masked-out
+ * entries count as -9999999) and the action index used. */
+typedef struct {
+  const float* q_on;          /* [b][q_ts][a][n_actions], dense; also the argmax's source (qmode 2) */
+  const float* q_tg;          /* NULL: one network */
+  int32_t q_ts, n_actions;
+  const int64_t* actions;     /* [b][t][a], strides act_sb, act_st (qmode 1) */
+  int64_t act_sb, act_st;
+  const int32_t* avail;       /* [b][t][a][n_actions], strides av_sb, av_st, or NULL */
+  int64_t av_sb, av_st;
+  int32_t qmode_on, qmode_tg; /* 1 or 2 */
+  float* qv_on;               /* out [B][T_on][A] */
+  float* qv_tg;               /* out [B][T_tg][A] */
+  float* qmax_on;             /* out [B][T_on][A] */
+  float* qmax_tg;             /* out [B][T_tg][A] */
+  int32_t* act_on;            /* out [B][T_on][A] */
+  int32_t* act_tg;            /* out [B][T_tg][A] */
+  int32_t B, T_on, T_tg, A;
+} t2o_qplex_select_args;
+int t2o_qplex_select(const t2o_qplex_select_args* a, void* stream);
+
+/* QPLEX forward of up to two networks in one launch on rows (b, t < T_*).
+ * parts: 1 = y_v, 2 = y_adv, 3 = y_v + y_adv (qmax and act are read with part 2). */
+typedef struct {
+  const float* params_on;
+  const float* params_tg;     /* NULL: one network */
+  const float* states;        /* [b][t][S], element strides st_sb, st_st */
+  int64_t st_sb, st_st;
+  const float* qv_on;         /* [B][T_on][A] */
+  const float* qv_tg;         /* [B][T_tg][A] */
+  const float* qmax_on;
+  const float* qmax_tg;
+  const int32_t* act_on;      /* values in [0, NA) */
+  const int32_t* act_tg;
+  float* y_on;                /* out [B][T_on] */
+  float* y_tg;                /* out [B][T_tg] */
+  int32_t B, T_on, T_tg, parts;
+  int32_t A, S, NA, H, HA, K;
+} t2o_qplex_fwd_args;
+int t2o_qplex_fwd(const t2o_qplex_fwd_args* a, void* stream);
+
+/* QPLEX backward of one network, of Σ gy · y(parts).  It recomputes the forward.
+ * phase 1: every row's dL/dqv = gy · w (0 without part 1) into gqv, and per block its
+ * hidden vector and the gradients of its pre-activation and output into work; phase 2:
+ * the weight gradients from work, as t2o_qplex_bwd_slabs(B, T) partial slabs
+ * [nslab][t2o_qplex_param_count] in the parameter order, each element written once by
+ * one workgroup in a fixed order (sum them with t2o_reduce_slabs).  phase 0: both. */
+typedef struct {
+  const float* params;
+  const float* states;
+  int64_t st_sb, st_st;
+  const float* qv;            /* [B][T][A] */
+  const float* qmax;          /* [B][T][A] */
+  const int32_t* act;         /* [B][T][A] */
+  const float* gy;            /* dL/dy [B][T] */
+  float* gqv;                 /* out [B][T][A] */
+  float* gslabs;              /* out [>= t2o_qplex_bwd_slabs][t2o_qplex_param_count] */
+  float* work;                /* t2o_qplex_bwd_work_floats floats, 16-byte aligned */
+  int64_t work_floats;
+  int32_t max_slabs;
+  int32_t phase;
+  int32_t parts;
+  int32_t B, T;
+  int32_t A, S, NA, H, HA, K;
+} t2o_qplex_bwd_args;
+int t2o_qplex_bwd(const t2o_qplex_bwd_args* a, void* stream);
+int t2o_qplex_bwd_slabs(int B, int T);                       /* T2O_EINVAL on a bad size */
+int64_t t2o_qplex_bwd_work_floats(int B, int T, int A, int H, int HA, int K);
 
 /* Diagnostic: runs the cross-lane primitives the kernels rely on (4-lane
  * all-reduces via ds_bpermute and via gfx950 permlane swaps, 16-lane DPP row

@@ -97,8 +97,19 @@ QmixFwdArgs = _args_class("QmixFwdArgs", 14, """params_on:P, params_tg:P, states
     y_on:P, y_tg:P, B:I, T_on:I, T_tg:I, A:I, S:I, M:I, H:I, pos_func:I, pos_beta:F, reserved_:I""")
 QmixBwdArgs = _args_class("QmixBwdArgs", 15, """params:P, states:P, st_sb:J, st_st:J, qv:P, gy:P, gqv:P, gslabs:P,
     work:P, work_floats:J, max_slabs:I, phase:I, B:I, T:I, A:I, S:I, M:I, H:I, pos_func:I, pos_beta:F""")
+# (id 16 stays unassigned too: t2o_args_sizeof(16) is published as -1)
+QplexSelectArgs = _args_class("QplexSelectArgs", 17, """q_on:P, q_tg:P, q_ts:I, n_actions:I, actions:P, act_sb:J,
+    act_st:J, avail:P, av_sb:J, av_st:J, qmode_on:I, qmode_tg:I, qv_on:P, qv_tg:P, qmax_on:P, qmax_tg:P, act_on:P,
+    act_tg:P, B:I, T_on:I, T_tg:I, A:I""")
+QplexFwdArgs = _args_class("QplexFwdArgs", 18, """params_on:P, params_tg:P, states:P, st_sb:J, st_st:J, qv_on:P,
+    qv_tg:P, qmax_on:P, qmax_tg:P, act_on:P, act_tg:P, y_on:P, y_tg:P, B:I, T_on:I, T_tg:I, parts:I, A:I, S:I, NA:I,
+    H:I, HA:I, K:I""")
+QplexBwdArgs = _args_class("QplexBwdArgs", 19, """params:P, states:P, st_sb:J, st_st:J, qv:P, qmax:P, act:P, gy:P,
+    gqv:P, gslabs:P, work:P, work_floats:J, max_slabs:I, phase:I, parts:I, B:I, T:I, A:I, S:I, NA:I, H:I, HA:I,
+    K:I""")
 ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs, TDQLambdaArgs,
-                NoiseArgs, NoisyFwdArgs, NoisyBwdArgs, NoisyWgradArgs, QSelectArgs, QmixFwdArgs, QmixBwdArgs)
+                NoiseArgs, NoisyFwdArgs, NoisyBwdArgs, NoisyWgradArgs, QSelectArgs, QmixFwdArgs, QmixBwdArgs,
+                QplexSelectArgs, QplexFwdArgs, QplexBwdArgs)
 NOISE_KINDS = {"learner_online": 0, "learner_target": 1, "runner": 2, "module": 3}  # include/t2omca.h T2O_NOISE_*
 EP_STATS = 10  # include/t2omca.h T2O_EP_STATS
 
@@ -158,6 +169,12 @@ EXPORTS = {
     "t2o_qmix_bwd_slabs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "t2o_qmix_bwd_work_floats": (ctypes.c_int64, [ctypes.c_int] * 4),
     "t2o_vdn_bwd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p]),
+    "t2o_qplex_param_count": (ctypes.c_int64, [ctypes.c_int] * 6),
+    "t2o_qplex_select": (ctypes.c_int, [ctypes.POINTER(QplexSelectArgs), ctypes.c_void_p]),
+    "t2o_qplex_fwd": (ctypes.c_int, [ctypes.POINTER(QplexFwdArgs), ctypes.c_void_p]),
+    "t2o_qplex_bwd": (ctypes.c_int, [ctypes.POINTER(QplexBwdArgs), ctypes.c_void_p]),
+    "t2o_qplex_bwd_slabs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "t2o_qplex_bwd_work_floats": (ctypes.c_int64, [ctypes.c_int] * 6),
     "t2o_probe_lane_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_scatter_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_xdl_hazards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -197,12 +214,16 @@ _OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats", "t2o_td_qlambda"
                            "t2o_noisy_head_wgrad",
                            # ... and the QMIX / VDN mixers
                            "t2o_q_select", "t2o_qmix_param_count", "t2o_qmix_fwd", "t2o_qmix_bwd",
-                           "t2o_qmix_bwd_slabs", "t2o_qmix_bwd_work_floats", "t2o_vdn_bwd"}
+                           "t2o_qmix_bwd_slabs", "t2o_qmix_bwd_work_floats", "t2o_vdn_bwd",
+                           # ... and the QPLEX mixer
+                           "t2o_qplex_param_count", "t2o_qplex_select", "t2o_qplex_fwd", "t2o_qplex_bwd",
+                           "t2o_qplex_bwd_slabs", "t2o_qplex_bwd_work_floats"}
 # argument structs of optional exports: no size to check where the export is absent
 _STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats", TDQLambdaArgs: "t2o_td_qlambda", NoiseArgs: "t2o_noise_normal",
                   NoisyFwdArgs: "t2o_noisy_head_fwd", NoisyBwdArgs: "t2o_noisy_head_bwd",
                   NoisyWgradArgs: "t2o_noisy_head_wgrad", QSelectArgs: "t2o_q_select",
-                  QmixFwdArgs: "t2o_qmix_fwd", QmixBwdArgs: "t2o_qmix_bwd"}
+                  QmixFwdArgs: "t2o_qmix_fwd", QmixBwdArgs: "t2o_qmix_bwd",
+                  QplexSelectArgs: "t2o_qplex_select", QplexFwdArgs: "t2o_qplex_fwd", QplexBwdArgs: "t2o_qplex_bwd"}
 
 _lib = None
 

@@ -353,6 +353,9 @@ extern "C" int t2o_args_sizeof(int which) {
     case T2O_ARGS_Q_SELECT: return (int)sizeof(t2o_q_select_args);
     case T2O_ARGS_QMIX_FWD: return (int)sizeof(t2o_qmix_fwd_args);
     case T2O_ARGS_QMIX_BWD: return (int)sizeof(t2o_qmix_bwd_args);
+    case T2O_ARGS_QPLEX_SELECT: return (int)sizeof(t2o_qplex_select_args);
+    case T2O_ARGS_QPLEX_FWD: return (int)sizeof(t2o_qplex_fwd_args);
+    case T2O_ARGS_QPLEX_BWD: return (int)sizeof(t2o_qplex_bwd_args);
     default: return -1;
   }
 }

@@ -63,6 +63,18 @@ These mixers read the state alone: no gradient reaches the agents' hidden states
 (detach_mixer_hidden has no effect), they are fp32 in both precisions, read their
 parameters straight from the flat buffers (no pack), and run the sequential update
 (pipeline=True is a ValueError; "auto" never pipelines them).
+
+A QPLEX mixer (modules.QPlexMixer, ``mixer.kind`` "qplex", PyMARL2's mixer: dmaq with
+its dmaq_qatten_learner and double_q) is the third of these flat mixers:
+
+  chosen / double-Q Q, each network's avail-masked         t2o_qplex_select (1 launch)
+      maximum of its own Q and the action used
+  both networks' y_v + y_adv                                t2o_qplex_fwd (1 launch, parts 3)
+  [q_lambda: the target Q, maxima at the batch's actions,   t2o_qplex_select, t2o_qplex_fwd (one network)]
+      and their mix
+  dL/dq_chosen = dL/dy · w, the rows' activations           t2o_qplex_bwd phase 1
+  weight-gradient slabs, their sum, the all-reduce          t2o_qplex_bwd phase 2, t2o_reduce_slabs: side stream
+No gradient reaches the maxima; ``learner.last_qmax`` keeps them beside ``last_qv``.
 """
 import dataclasses
 import os
@@ -77,7 +89,7 @@ from .state import check_fields, copy_checked
 
 
 OPTIMIZERS = {"adam": "Adam", "rmsprop": "RMSprop"}  # TDLearner(optimizer=...): the torch.optim class of opt.th
-MIXERS = ("transformer", "qmix", "vdn")  # modules.TransformerMixer / QMixer / VDNMixer .kind
+MIXERS = ("transformer", "qmix", "vdn", "qplex")  # modules.TransformerMixer / QMixer / VDNMixer / QPlexMixer .kind
 
 
 def _mixer_kind_of(state_dict):
@@ -86,6 +98,8 @@ def _mixer_kind_of(state_dict):
         return "vdn"
     if "hyper_w1.0.weight" in state_dict:
         return "qmix"
+    if "hyper_w_final.0.weight" in state_dict:
+        return "qplex"
     if any(k.startswith("transformer.tblocks") for k in state_dict):
         return "transformer"
     return None
@@ -161,7 +175,7 @@ class TDLearner:
         self.sa = dataclasses.replace(agent.shape, prec=prec)
         if self.mixer_kind == "transformer":
             self.sm = dataclasses.replace(mixer.shape, prec=prec)
-        else:  # ops.QmixShape (fp32 in both precisions), or None: VDN has no parameters
+        else:  # ops.QmixShape / QplexShape (fp32 in both precisions), or None: VDN has no parameters
             self.sm = getattr(mixer, "shape", None)
         # a noisy agent's flat parameters: the plain agent's na_net floats (what the packs and
         # the fused kernels read), then the head's NA·(E+1) sigmas
@@ -343,7 +357,7 @@ class TDLearner:
         framework.  As PyMARL2's NQLearner does, the target agent is reloaded from
         agent.th and the target mixer is left as it is; opt.th is optional, and one
         written by the other optimiser is a ValueError naming both, and so is a mixer.th
-        of another kind of mixer (told by its keys: transformer, qmix, or vdn's empty
+        of another kind of mixer (told by its keys: transformer, qmix, qplex, or vdn's empty
         dict).  opt.th follows the
         modules' parameter order (a noisy agent: q_basic.u_w, u_b, s_w, s_b last of the
         agent's); an agent.th of the other head, or an opt.th whose per-parameter shapes
@@ -685,7 +699,7 @@ class TDLearner:
         return self._finish(episode_num, td, o_on, t_env, term, filled)
 
     def _train_flat_mixer(self, obs, state, act, avail, reward, term, filled, w, t_env, episode_num):
-        """train() with a QMIX or VDN mixer (module docstring): the agent unroll, the TD
+        """train() with a QMIX, VDN or QPLEX mixer (module docstring): the agent unroll, the TD
         loss, the agent BPTT, the optimiser step and the statistics are the transformer
         path's; steps 2 and 4 are the select kernel and the flat mixers' kernels.  The
         mixers read the state alone, so gh is None: no gradient reaches the agents'
@@ -693,7 +707,7 @@ class TDLearner:
         B, T1, A, _ = obs.shape
         T = T1 - 1
         dev = self.device
-        vdn = self.mixer_kind == "vdn"
+        vdn, qplex = self.mixer_kind == "vdn", self.mixer_kind == "qplex"
         state = state.reshape(B, T1, -1) if state.dim() != 3 else state
         p_on, p_tg = self.params[self.na:], self.target_params[self.na:]
         main = torch.cuda.current_stream(dev)
@@ -716,15 +730,31 @@ class TDLearner:
         # 2. chosen Q (t < T) and double-Q selection (t <= T); VDN's mix is the kernel's row sum
         qv_on, qv_tg = self._buf("qv_on", (B, T, A)), self._buf("qv_tg", (B, T1, A))
         y_on, y_tg = torch.empty(B, T, device=dev), torch.empty(B, T1, device=dev)
-        ops.q_select(q_on, qmode_on=1, actions=act, avail=avail, T_on=T, q_tg=q_tg, qmode_tg=2, T_tg=T1,
-                     outs=((qv_on, y_on if vdn else None), (qv_tg, y_tg if vdn else None)), timer=self.timer)
-        if not vdn:
+        if qplex:
+            # ... and each network's avail-masked maximum of its own Q and the action used (int32)
+            sel_on = (qv_on, self._buf("qm_on", (B, T, A)), self._buf("u_on", (B, T, A)).view(torch.int32))
+            sel_tg = (qv_tg, self._buf("qm_tg", (B, T1, A)), self._buf("u_tg", (B, T1, A)).view(torch.int32))
+            ops.qplex_select(q_on, qmode_on=1, actions=act, avail=avail, T_on=T, q_tg=q_tg, qmode_tg=2, T_tg=T1,
+                             outs=(sel_on, sel_tg), timer=self.timer)
+            ops.qplex_fwd(self.sm, p_on, state, *sel_on, params_tg=p_tg, qv_tg=sel_tg[0], qmax_tg=sel_tg[1],
+                          act_tg=sel_tg[2], parts=3, outs=(y_on, y_tg), timer=self.timer)
+            self.last_qmax = (sel_on[1], sel_tg[1])  # (buffers the next update reuses, as last_qv)
+        else:
+            ops.q_select(q_on, qmode_on=1, actions=act, avail=avail, T_on=T, q_tg=q_tg, qmode_tg=2, T_tg=T1,
+                         outs=((qv_on, y_on if vdn else None), (qv_tg, y_tg if vdn else None)), timer=self.timer)
+        if not vdn and not qplex:
             ops.qmix_fwd(self.sm, p_on, state, qv_on, params_tg=p_tg, qv_tg=qv_tg, outs=(y_on, y_tg), timer=self.timer)
         self.last_qv = (qv_on, qv_tg)  # what the mixers read (buffers the next update reuses)
         if self.q_lambda:  # the target mixer on the target Q at the batch's actions, t < T
             qv_tk, y_tk = self._buf("qv_tk", (B, T, A)), torch.empty(B, T, device=dev)
-            ops.q_select(q_tg, qmode_on=1, actions=act, T_on=T, outs=(qv_tk, y_tk if vdn else None), timer=self.timer)
-            if not vdn:
+            if qplex:  # ... with the target network's own maxima
+                sel_tk = (qv_tk, self._buf("qm_tk", (B, T, A)), self._buf("u_tk", (B, T, A)).view(torch.int32))
+                ops.qplex_select(q_tg, qmode_on=1, actions=act, avail=avail, T_on=T, outs=sel_tk, timer=self.timer)
+                ops.qplex_fwd(self.sm, p_tg, state, *sel_tk, parts=3, outs=y_tk, timer=self.timer)
+            else:
+                ops.q_select(q_tg, qmode_on=1, actions=act, T_on=T, outs=(qv_tk, y_tk if vdn else None),
+                             timer=self.timer)
+            if not vdn and not qplex:
                 ops.qmix_fwd(self.sm, p_tg, state, qv_tk, outs=y_tk, timer=self.timer)
         # 3. TD(λ) / Q(λ) targets and the loss (Σ mask lands in grad[-1], cleared on the side stream)
         main.wait_event(grad_clear)
@@ -740,6 +770,12 @@ class TDLearner:
         mixer_dw = None
         if vdn:
             ops.vdn_bwd(td["gq"], gqv=gqv, timer=self.timer)
+        elif qplex:
+            slabs = self._slab("qplex", ops.qplex_slab_count(B, T) * self.nm)
+            work = self._slab("qplex_work", ops.qplex_work_floats(self.sm, B, T))
+            mixer_dw, _, _, nslab = ops.qplex_bwd(self.sm, p_on, state, *sel_on, td["gq"], parts=3, gqv=gqv,
+                                                  slabs=slabs, work=work, timer=self.timer, launcher=True)
+            mixer_dw(1)
         else:
             slabs = self._slab("qmix", ops.qmix_slab_count(B, T) * self.nm)
             work = self._slab("qmix_work", ops.qmix_work_floats(self.sm, B, T))

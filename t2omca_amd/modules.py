@@ -437,12 +437,118 @@ class VDNMixer(nn.Module):
         return _VDNStep.apply(qvals)
 
 
+class _QPlexStep(torch.autograd.Function):
+    """QPlexMixer.forward on the HIP kernels (t2o_qplex_fwd / t2o_qplex_bwd): `parts` 1 is
+    y_v, 2 is y_adv.  The parameters enter as separate inputs, their gradients leave as
+    views of one flat buffer (the slab sum, in the parameter order).  No gradient reaches
+    the maxima, and none reaches q through y_adv (its c = w (q − m) is a constant)."""
+
+    @staticmethod
+    def forward(ctx, shape, parts, qvals, states, qmax, act, *params):
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1) for p in params])
+        qv = qvals.detach().contiguous()
+        st = states.detach()
+        if st.stride(2) != 1:
+            st = st.contiguous()
+        y = ops.qplex_fwd(shape, flat, st, qv, qmax, act, parts=parts)
+        ctx.save_for_backward(flat, qv, st, qmax, act)
+        ctx.shape, ctx.parts, ctx.param_shapes = shape, parts, [p.shape for p in params]
+        return y.unsqueeze(2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        flat, qv, st, qmax, act = ctx.saved_tensors
+        gqv, slabs, nslab = ops.qplex_bwd(ctx.shape, flat, st, qv, qmax, act, gy.reshape(qv.shape[:2]).contiguous(),
+                                          parts=ctx.parts)
+        gflat = ops.reduce_slabs(slabs, nslab, torch.empty_like(flat))
+        return (None, None, gqv, None, None, None) + _split_like(gflat, ctx.param_shapes)
+
+
+class _SIWeight(nn.Module):
+    """The parameter tree of PyMARL2's dmaq_si_weight.DMAQ_SI_Weight at adv_hypernet_layers 2."""
+
+    def __init__(self, A, S, NA, HA, K):
+        super().__init__()
+        def net(n_in, n_out):
+            return nn.Sequential(nn.Linear(n_in, HA), nn.ReLU(), nn.Linear(HA, n_out))
+        self.key_extractors = nn.ModuleList([net(S, 1) for _ in range(K)])
+        self.agents_extractors = nn.ModuleList([net(S, A) for _ in range(K)])
+        self.action_extractors = nn.ModuleList([net(S + A * NA, A) for _ in range(K)])
+
+
+class QPlexMixer(nn.Module):
+    """The QPLEX duelling mixer, PyMARL2's modules/mixers/dmaq_general.py `DMAQer` with
+    dmaq_si_weight.py at qplex.yaml's defaults.  It does not ship with the reference
+    (n_transf_mixer.py only): this is the DECLARED definition of DESIGN.md §5,
+    parity-unpinned.  Per (episode, step) row, with sg the stop-gradient,
+
+        w = |hyper_w_final(s)| + 1e-10      v = V(s)
+        λ = Σ_k (|key_k(s)| + 1e-10) · sigmoid(agents_k(s)) · sigmoid(action_k([s ; onehot(u)]))
+        y_v = Σ_a (w_a q_a + v_a)           y_adv = Σ_a sg[w_a (q_a − m_a)] (λ_a − 1)
+
+    with H = args.hypernet_embed (64), HA = args.adv_hypernet_embed (64), K =
+    args.num_kernel (4), the state width S = prod(args.state_shape) (default: the state's
+    entities x state_entity_feats) and NA = args.n_actions.  Torch's default
+    initialisation.  What the kernels do not take is a ValueError here."""
+
+    kind = "qplex"
+    custom_space = True  # the learner reads the state whatever state_entity_mode says
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.n_agents = A = int(args.n_agents)
+        self.n_actions = NA = int(args.n_actions)
+        self.hypernet_embed = H = int(getattr(args, "hypernet_embed", 64))
+        self.adv_hypernet_embed = HA = int(getattr(args, "adv_hypernet_embed", 64))
+        self.num_kernel = K = int(getattr(args, "num_kernel", 4))
+        state_shape = getattr(args, "state_shape", None)
+        if state_shape is None:
+            state_shape = getattr(args, "n_entities_state", args.n_entities) * args.state_entity_feats
+        self.state_dim = S = int(torch.Size([state_shape] if isinstance(state_shape, int) else state_shape).numel())
+        layers = int(getattr(args, "adv_hypernet_layers", 2))
+        weighted, minus_one = getattr(args, "weighted_head", True), getattr(args, "is_minus_one", True)
+        if not (1 <= A <= 64 and 1 <= S <= 1024 and 1 <= NA <= 16 and H in (32, 64) and HA in (32, 64) and
+                1 <= K <= 10 and layers == 2 and weighted is True and minus_one is True):
+            raise ValueError(f"QPlexMixer: n_agents={A}, state width {S}, n_actions={NA}, hypernet_embed={H}, "
+                             f"adv_hypernet_embed={HA}, num_kernel={K}, adv_hypernet_layers={layers}, "
+                             f"weighted_head={weighted}, is_minus_one={minus_one}: the QPLEX kernels take "
+                             f"{ops.QPLEX_LIMITS}")
+        self.hyper_w_final = nn.Sequential(nn.Linear(S, H), nn.ReLU(), nn.Linear(H, A))
+        self.V = nn.Sequential(nn.Linear(S, H), nn.ReLU(), nn.Linear(H, A))
+        self.si_weight = _SIWeight(A, S, NA, HA, K)
+        self.shape = ops.QplexShape(A, S, NA, H, HA, K)
+
+    def forward(self, agent_qs, states, actions=None, max_q_i=None, is_v=False):
+        """PyMARL2's DMAQer.forward: is_v=True -> y_v [b, T, 1]; is_v=False -> y_adv, with
+        `actions` one-hot [b, T, A, NA] or an index [b, T, A] and `max_q_i` [b, T, A]."""
+        if not agent_qs.is_cuda:
+            raise RuntimeError("QPlexMixer.forward needs HIP-device tensors (no CPU fallback)")
+        b, T = agent_qs.shape[:2]
+        A = self.n_agents
+        q = agent_qs.reshape(b, T, A)
+        if is_v:  # (the kernels read both arrays in either part: zeros, which y_v does not depend on)
+            qmax = torch.zeros(b, T, A, device=q.device)
+            act = torch.zeros(b, T, A, device=q.device, dtype=torch.int32)
+        else:
+            if actions is None or max_q_i is None:
+                raise ValueError("QPlexMixer.forward: is_v=False needs actions and max_q_i")
+            idx = actions.argmax(dim=3) if actions.dim() == 4 and actions.shape[3] == self.n_actions else actions
+            act = idx.reshape(b, T, A).to(torch.int32).contiguous()
+            qmax = max_q_i.detach().reshape(b, T, A).float().contiguous()
+        return _QPlexStep.apply(self.shape, 1 if is_v else 2, q, states.reshape(b, T, self.state_dim), qmax, act,
+                                *self.parameters())
+
+
 def make_mixer(args):
-    """args.mixer: "qmix" -> QMixer, "vdn" -> VDNMixer, absent or anything else ->
-    the reference's TransformerMixer."""
+    """args.mixer: "qmix" -> QMixer, "vdn" -> VDNMixer, "dmaq" (PyMARL2's name) or "qplex"
+    -> QPlexMixer, absent or anything else -> the reference's TransformerMixer."""
     name = getattr(args, "mixer", None)
     if name == "qmix":
         return QMixer(args)
     if name == "vdn":
         return VDNMixer()
+    if name in ("dmaq", "qplex"):
+        return QPlexMixer(args)
     return TransformerMixer(args)

@@ -1022,3 +1022,211 @@ def vdn_bwd(gy, gqv=None, A=None, timer=None):
     check(lib().t2o_vdn_bwd(_p(gy), _p(gqv), B, T, gqv.shape[2], stream_ptr(gy.device)), "vdn_bwd")
     _mark(timer, "end:vdn_bwd")
     return gqv
+
+
+# ---- the QPLEX duelling mixer (include/t2omca.h t2o_qplex_*) ----
+
+@dataclass(frozen=True)
+class QplexShape:
+    """Sizes of a QPlexMixer (modules.QPlexMixer): agents, state width, actions,
+    hypernet_embed H, adv_hypernet_embed HA and num_kernel K."""
+    A: int
+    S: int
+    NA: int
+    H: int = 64
+    HA: int = 64
+    K: int = 4
+
+    @property
+    def n_params(self):
+        return int(lib().t2o_qplex_param_count(self.A, self.S, self.NA, self.H, self.HA, self.K))
+
+    @property
+    def agents(self):
+        return self.A
+
+
+QPLEX_LIMITS = ("1 <= n_agents <= 64, 1 <= state width <= 1024, 1 <= n_actions <= 16, hypernet_embed and "
+                "adv_hypernet_embed in {32, 64}, 1 <= num_kernel <= 10, adv_hypernet_layers == 2, weighted_head and "
+                "is_minus_one True")
+
+
+def qplex_param_blocks(A, S, NA, H=64, HA=64, K=4):
+    """(state_dict key, shape) of a QPlexMixer's parameters in their flat order."""
+    def net(name, n_in, hid, n_out):
+        return [(f"{name}.0.weight", (hid, n_in)), (f"{name}.0.bias", (hid,)), (f"{name}.2.weight", (n_out, hid)),
+                (f"{name}.2.bias", (n_out,))]
+    out = net("hyper_w_final", S, H, A) + net("V", S, H, A)
+    for name, n_in, n_out in (("key_extractors", S, 1), ("agents_extractors", S, A),
+                              ("action_extractors", S + A * NA, A)):
+        for k in range(K):
+            out += net(f"si_weight.{name}.{k}", n_in, HA, n_out)
+    return out
+
+
+def _i32c(name, t, shape):
+    if not t.is_cuda:
+        raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{name}: expected a dense int32 tensor of shape {tuple(shape)}, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def qplex_select(q_on, *, qmode_on=1, actions=None, avail=None, T_on=None, q_tg=None, qmode_tg=2, T_tg=None,
+                 outs=None, timer=None):
+    """q_select for the QPLEX mixer (t2o_qplex_select): per network the selected Q, the
+    avail-masked maximum of the network's own Q and the action index used (int32), each
+    [B, T_*, A].  Arguments as q_select.  Returns (qv, qmax, act), or a pair of them with
+    two networks; outs: the same structure of preallocated dense tensors."""
+    _f32c("qplex_select: q_on", q_on)
+    B, q_ts, A, NA = q_on.shape
+    T_on = int(T_on or q_ts)
+    two = q_tg is not None
+    if two:
+        _f32c("qplex_select: q_tg", q_tg, (B, q_ts, A, NA))
+        T_tg = int(T_tg or q_ts)
+    if qmode_on not in (1, 2) or (two and qmode_tg not in (1, 2)):
+        raise ValueError("qplex_select: qmode must be 1 (gather at the actions) or 2 (double-Q argmax)")
+    if actions is not None:
+        _i64c("qplex_select: actions", actions)
+    elif qmode_on == 1 or (two and qmode_tg == 1):
+        raise ValueError("qplex_select: qmode 1 needs the actions")
+    if avail is not None:
+        if not avail.is_cuda:
+            raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+        if avail.dtype != torch.int32 or avail.stride(3) != 1 or avail.stride(2) != NA:
+            raise TypeError("qplex_select: avail must be int32 [B, >= T, A, NA] with dense [A, NA] rows")
+    dev = q_on.device
+
+    def alloc(T):
+        return (torch.empty(B, T, A, device=dev), torch.empty(B, T, A, device=dev),
+                torch.empty(B, T, A, device=dev, dtype=torch.int32))
+    if outs is None:
+        outs = (alloc(T_on), alloc(T_tg)) if two else alloc(T_on)
+    o_on, o_tg = outs if two else (outs, (None, None, None))
+    for o, T in ((o_on, T_on),) + (((o_tg, T_tg),) if two else ()):
+        _f32c("qplex_select: qv", o[0], (B, T, A))
+        _f32c("qplex_select: qmax", o[1], (B, T, A))
+        _i32c("qplex_select: act", o[2], (B, T, A))
+    act_sb, act_st = _mstrides(actions)
+    av_sb, av_st = _mstrides(avail)
+    a = _lib.QplexSelectArgs(q_on=_p(q_on), q_tg=_p(q_tg), q_ts=q_ts, n_actions=NA, actions=_p(actions),
+                             act_sb=act_sb, act_st=act_st, avail=_p(avail), av_sb=av_sb, av_st=av_st,
+                             qmode_on=qmode_on, qmode_tg=qmode_tg if two else 0, qv_on=_p(o_on[0]), qv_tg=_p(o_tg[0]),
+                             qmax_on=_p(o_on[1]), qmax_tg=_p(o_tg[1]), act_on=_p(o_on[2]), act_tg=_p(o_tg[2]),
+                             B=B, T_on=T_on, T_tg=T_tg if two else 0, A=A)
+    _mark(timer, "begin:qplex_select")
+    check(lib().t2o_qplex_select(ctypes.byref(a), stream_ptr(dev)), "qplex_select")
+    _mark(timer, "end:qplex_select")
+    return outs
+
+
+def _qplex_rows(name, shape, qv, qmax, act, need_adv=True):
+    B, T, A = qv.shape
+    _f32c(f"{name}: qv", qv, (B, T, shape.A))
+    if qmax is None or act is None:
+        if need_adv:
+            raise ValueError(f"{name}: the advantage part needs qmax and act")
+        return
+    _f32c(f"{name}: qmax", qmax, (B, T, A))
+    _i32c(f"{name}: act", act, (B, T, A))
+
+
+def qplex_fwd(shape: QplexShape, params_on, states, qv_on, qmax_on=None, act_on=None, *, params_tg=None, qv_tg=None,
+              qmax_tg=None, act_tg=None, parts=3, outs=None, timer=None):
+    """QPLEX forward (t2o_qplex_fwd) of one or two networks in one launch.  params_*:
+    the mixer's flat parameters (dense float32, shape.n_params, any 4-byte alignment);
+    states [B, >= T, S] (any episode / step strides); qv_*, qmax_* float32 and act_*
+    int32, [B, T_*, A] dense.  parts: 1 = y_v, 2 = y_adv, 3 = their sum.  Returns y_on
+    [B, T_on], or (y_on, y_tg)."""
+    if parts not in (1, 2, 3):
+        raise ValueError("qplex_fwd: parts must be 1 (y_v), 2 (y_adv) or 3 (both)")
+    B, T_on, A = qv_on.shape
+    _f32c("qplex_fwd: params_on", params_on, (shape.n_params,))
+    _qplex_rows("qplex_fwd", shape, qv_on, qmax_on, act_on, parts & 2)
+    _qmix_states("qplex_fwd", states, B, shape.S)
+    two = params_tg is not None
+    T_tg = 0
+    if two:
+        T_tg = qv_tg.shape[1]
+        _f32c("qplex_fwd: params_tg", params_tg, (shape.n_params,))
+        _qplex_rows("qplex_fwd", shape, qv_tg, qmax_tg, act_tg, parts & 2)
+    if states.shape[1] < max(T_on, T_tg):
+        raise ValueError(f"qplex_fwd: {max(T_on, T_tg)} steps, the states cover {states.shape[1]}")
+    dev = qv_on.device
+    if outs is None:
+        outs = (torch.empty(B, T_on, device=dev), torch.empty(B, T_tg, device=dev)) if two else \
+            torch.empty(B, T_on, device=dev)
+    y_on, y_tg = outs if two else (outs, None)
+    _f32c("qplex_fwd: y_on", y_on, (B, T_on))
+    if two:
+        _f32c("qplex_fwd: y_tg", y_tg, (B, T_tg))
+    a = _lib.QplexFwdArgs(params_on=_p(params_on), params_tg=_p(params_tg), states=_p(states), st_sb=states.stride(0),
+                          st_st=states.stride(1), qv_on=_p(qv_on), qv_tg=_p(qv_tg), qmax_on=_p(qmax_on),
+                          qmax_tg=_p(qmax_tg), act_on=_p(act_on), act_tg=_p(act_tg), y_on=_p(y_on), y_tg=_p(y_tg),
+                          B=B, T_on=T_on, T_tg=T_tg, parts=parts, A=shape.A, S=shape.S, NA=shape.NA, H=shape.H,
+                          HA=shape.HA, K=shape.K)
+    _mark(timer, "begin:qplex_fwd")
+    check(lib().t2o_qplex_fwd(ctypes.byref(a), stream_ptr(dev)), "qplex_fwd")
+    _mark(timer, "end:qplex_fwd")
+    return outs
+
+
+def qplex_slab_count(B, T):
+    n = int(lib().t2o_qplex_bwd_slabs(int(B), int(T)))
+    if n < 1:
+        raise ValueError(f"qplex_slab_count: bad shape B={B} T={T}")
+    return n
+
+
+def qplex_work_floats(shape: QplexShape, B, T):
+    n = int(lib().t2o_qplex_bwd_work_floats(int(B), int(T), shape.A, shape.H, shape.HA, shape.K))
+    if n < 1:
+        raise ValueError(f"qplex_work_floats: bad shape B={B} T={T} {shape}")
+    return n
+
+
+def qplex_bwd(shape: QplexShape, params, states, qv, qmax, act, gy, *, parts=3, gqv=None, slabs=None, work=None,
+              timer=None, launcher=False):
+    """QPLEX backward (t2o_qplex_bwd) of one network, of Σ gy · y(parts): dL/dqv
+    [B, T, A] (= gy · w; zeros without part 1) and the partial weight-gradient slabs
+    [qplex_slab_count(B, T), n_params] (sum them with reduce_slabs).  Returns (gqv, slabs,
+    nslab); launcher: (go, gqv, slabs, nslab) with go(phase) — 1 the rows (gqv and the
+    work buffer), 2 the weight gradients."""
+    if parts not in (1, 2, 3):
+        raise ValueError("qplex_bwd: parts must be 1 (y_v), 2 (y_adv) or 3 (both)")
+    B, T, A = qv.shape
+    _f32c("qplex_bwd: params", params, (shape.n_params,))
+    _qplex_rows("qplex_bwd", shape, qv, qmax, act)
+    _f32c("qplex_bwd: gy", gy, (B, T))
+    _qmix_states("qplex_bwd", states, B, shape.S)
+    if states.shape[1] < T:
+        raise ValueError(f"qplex_bwd: {T} steps, the states cover {states.shape[1]}")
+    dev = qv.device
+    nslab, nwork = qplex_slab_count(B, T), qplex_work_floats(shape, B, T)
+    if gqv is None:
+        gqv = torch.empty(B, T, A, device=dev)
+    if slabs is None:
+        slabs = torch.empty(nslab * shape.n_params, device=dev)
+    if work is None:
+        work = torch.empty(nwork, device=dev)
+    _f32c("qplex_bwd: gqv", gqv, (B, T, A))
+    _f32c("qplex_bwd: slabs", slabs)
+    _f32c("qplex_bwd: work", work)
+    if slabs.numel() < nslab * shape.n_params or work.numel() < nwork:
+        raise ValueError("qplex_bwd: the slab or work buffer is too small")
+    a = _lib.QplexBwdArgs(params=_p(params), states=_p(states), st_sb=states.stride(0), st_st=states.stride(1),
+                          qv=_p(qv), qmax=_p(qmax), act=_p(act), gy=_p(gy), gqv=_p(gqv), gslabs=_p(slabs),
+                          work=_p(work), work_floats=work.numel(), max_slabs=slabs.numel() // shape.n_params,
+                          parts=parts, B=B, T=T, A=shape.A, S=shape.S, NA=shape.NA, H=shape.H, HA=shape.HA, K=shape.K)
+    fn = lib().t2o_qplex_bwd
+
+    def go(phase=0):
+        a.phase = int(phase)
+        _mark(timer, "begin:qplex_bwd")
+        check(fn(ctypes.byref(a), stream_ptr(dev)), "qplex_bwd")
+        _mark(timer, "end:qplex_bwd")
+    if launcher:
+        return go, gqv, slabs, nslab
+    go(0)
+    return gqv, slabs, nslab

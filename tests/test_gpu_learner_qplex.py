@@ -1,0 +1,352 @@
+"""GPU: whole TD updates with the QPLEX mixer (TDLearner with modules.QPlexMixer, mixer:
+dmaq) against the fp64 oracle, whose mixer and rows are tests/qplex_model's
+restatement of PyMARL2's dmaq_qatten_learner with double_q (substituted for
+ref_learner.td_forward with monkeypatch.setattr, so that oracle_td_tie_aware /
+check_update work unchanged).
+
+Modules: the agent drawn with torch.manual_seed(0) (test_gpu_learner_mixers' agent, whose
+argmax figures are known), the mixer with torch.manual_seed(MIXER_SEED = 1) (why: "fitness
+in float32" below).  Batch:
+make_batch(seed 3) drawn on the CPU, masked_avail seed 103.  The targets are perturbed by
+0.1·N(0, 1) (seed 1), ten times test_gpu_learner_masks.perturb_targets' scale: under 0.01
+the target network's Q at the online argmax is its own masked maximum in all but 5-8 %
+of the entries, and QPLEX's advantage term (q − m) would go unchecked on the target rows.
+
+Conditions, from the oracle alone, asserted in every fp32 case and printed:
+  * check_update's own: argmax moved >= 0.25, top-two gap >= 1e-4;
+  * the share of (row, agent) entries with q != m is >= 0.25 on the online rows AND on
+    the target rows (NEQ_SHARE);
+  * every parameter block's share of the largest gradient >= grad_blocks.FIT_SHARE
+    (assert_blocks_fp32's fitness condition).
+
+The mixer's seed.  Drawn straight after the agent under seed 0, the mixer gives at (8, 6, 5)
+a key extractor's last bias (key_extractors.1.2.bias) a share of 5.7e-5: fit by FIT_SHARE,
+but that gradient is a sum over the rows of signed terms ~1e3 times their sum, which
+float32 arithmetic in any order loses.  The fp64 oracle itself, evaluated in float32 on
+the CPU, is 9.1e-6 off on that block and <= 1e-6 on every other; the kernels measured
+5.6e-5 there and <= 2.4e-6 elsewhere.  With the mixer drawn under seeds 1, 2, 3 the float32
+oracle's worst block over this file's fp32 cases is 1.05e-6, 7.8e-7, 8.4e-7 (one evaluation
+scatters: the (3, 5, 4) case gave 1.05e-6 on one host and 3.6e-6 on another, so the figure
+chose the seed and is not asserted).  Seed 1 is the first such draw; every condition above
+was computed for it on the CPU before any GPU run.
+
+Bars (the project's): fp32 qtot, targets, priorities 1e-5; gradient 3e-5 flat and per
+parameter block; bf16 (agent in bf16, mixer fp32): finite, qtot against the fp64 mixer on
+last_qv / last_qmax below 1e-5, and a second update from the snapshot bit-equal.
+
+MEASURED on an MI355X, with this file's own draws (no ReLU tie overridden):
+
+  (A, B, T)    moved / gap       q != m on / tg   smallest share   qtot    targets prio    grad    (worst block)
+  (3, 5, 4)    0.693 / 3.65e-3   0.817 / 0.373    2.2e-4           2.7e-7  1.9e-7  1.1e-7  1.7e-7  (1.3e-6)
+  (8, 6, 5)    0.590 / 1.17e-3   0.771 / 0.392    1.9e-4           1.7e-7  2.3e-7  1.2e-7  1.9e-7  (6.4e-7)
+  (16, 3, 4)   0.554 / 2.94e-3   0.833 / 0.388    2.6e-4           3.0e-7  1.8e-7  8.3e-8  1.1e-7  (8.2e-7)
+  (64, 2, 3)   0.557 / 1.21e-3   0.768 / 0.428    1.3e-4           4.3e-7  2.9e-7  1.1e-7  1.9e-7  (1.8e-6)
+  q_lambda, rmsprop, noisy, pair, overlap=False at (8, 6, 5): every figure <= 4.4e-7, blocks <= 6.4e-7; qtot_taken
+  2.9e-7, qtot_tgt 1.8e-7; RMSprop transition square_avg 1.3e-7, p 6.0e-8 (bar 1.6e-7).  The rows the mixer read
+  (last_qv, last_qmax) against the oracle's <= 5.2e-7.  bf16: qtot against the fp64 mixer on last_qv / last_qmax
+  2.1e-7.  Two gloo ranks against the full batch: gradient 1.7e-7, parameters 2.2e-7.  (With the mixer drawn
+  straight after the agent under seed 100 the same comparison gave gradient 1.8e-7, parameters 2.0e-6: one AGENT
+  weight, unifyheads.weight of block 1, whose full-batch gradient is -8.7e-8, nine times Adam's eps, and differs by
+  1.9e-9 between the two summation orders; Adam's first step lr·g / (|g| + eps) turns that into 2.0e-6.)
+  Every agent gradient is 0.31 - 0.96 (normwise) away from the QMIX learner's on the same batch.
+"""
+import os
+import socket
+
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from tests import qplex_model
+from tests.gpu_util import normwise, require_gpu, split_flat
+from tests.qlambda_model import rmsprop_errors, rmsprop_ref
+from tests.test_gpu_generic import _args, _cfg_of
+from tests.test_gpu_learner_masks import SEED, TOL, Snapshot, check_update, masked_batch, to_cuda, update
+from tests.test_gpu_learner_qlambda import _preconditions
+
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(3, 5, 4), (8, 6, 5), (16, 3, 4), (64, 2, 3)]
+OPT = (8, 6, 5)
+TARGET_SCALE = 0.1
+NEQ_SHARE = 0.25
+MIXER_SEED = 1
+NA = 5
+
+
+@pytest.fixture(autouse=True)
+def _kernel_family(monkeypatch):
+    monkeypatch.setenv("T2O_GENERIC", "0")
+    monkeypatch.delenv("T2O_MIXER_SPLIT", raising=False)
+
+
+def modules(cfg, kind="dmaq", noisy=False, device="cuda", seed=0, mixer_seed=None):
+    """The agent drawn with torch.manual_seed(seed), the mixer with mixer_seed (default seed + MIXER_SEED)."""
+    from t2omca_amd.modules import TransformerAgent, make_mixer
+    torch.manual_seed(seed)
+    args = _args(cfg, device=str(device))
+    args.mixer = kind
+    if noisy:
+        args.action_selector = "noisy-new"
+    agent = TransformerAgent(None, args).to(device)
+    torch.manual_seed(seed + MIXER_SEED if mixer_seed is None else mixer_seed)
+    return agent, make_mixer(args).to(device)
+
+
+def make_learner(cfg, kind="dmaq", noisy=False, **kw):
+    from t2omca_amd.learner import TDLearner
+    agent, mixer = modules(cfg, kind, noisy)
+    pa = {k: v.detach().cpu().double() for k, v in agent.state_dict().items()}
+    pm = {k: v.detach().cpu().double() for k, v in mixer.state_dict().items()}
+    return TDLearner(agent, mixer, **kw), pa, pm
+
+
+def target_noise(n, seed=1):
+    return TARGET_SCALE * torch.randn(n, generator=torch.Generator().manual_seed(seed))
+
+
+def perturb_targets(learner):
+    learner.target_params.add_(target_noise(learner.target_params.numel()).cuda())
+    learner._pack_targets()
+
+
+def neq_shares(ex):
+    """Share of (row, agent) entries with q != m on the oracle's online and target rows."""
+    return tuple(float((q != m).double().mean()) for q, m in (ex["rows_on"], ex["rows_tg"]))
+
+
+def _oracle(monkeypatch, **kw):
+    from oracle import ref_learner
+    monkeypatch.setattr(ref_learner, "td_forward", qplex_model.td_forward_qplex(**kw))
+
+
+def _update(monkeypatch, tag, A, B, T, *, noisy=False, q_lambda=False, **kw):
+    """One update from perturbed targets against the substituted oracle at the fp32 bars."""
+    cfg = _cfg_of(A)
+    learner, pa, pm = make_learner(cfg, noisy=noisy, q_lambda=q_lambda, **kw)
+    assert learner.mixer_kind == "qplex" and not learner._pipelined(B)
+    assert learner.nm == sum(v.numel() for v in pm.values()) and list(pm) == qplex_model.keys(4)
+    perturb_targets(learner)
+    pat, pmt = split_flat(learner.target_params, pa, pm)
+    cpu, w = masked_batch(A, B, T, SEED)
+    snap = Snapshot(learner)
+    out, info = update(learner, to_cuda(cpu), w.cuda())
+    noise = None
+    if noisy:
+        noise = tuple((e[0].cpu().double(), e[1].cpu().double()) for e in learner.last_noise)
+    _oracle(monkeypatch, q_lambda=q_lambda, noise=noise)
+    errs, g, ex = check_update(f"{tag} qplex", learner, pa, pm, cfg, cpu, w, out, pa_tgt=pat, pm_tgt=pmt)
+    s_on, s_tg = neq_shares(ex)
+    print(f"{tag} qplex: share of q != m online {s_on:.3f} target {s_tg:.3f}")
+    assert s_on >= NEQ_SHARE and s_tg >= NEQ_SHARE, (s_on, s_tg)
+    # the rows the mixer read are the oracle's
+    (qv_on, qv_tg), (qm_on, qm_tg) = learner.last_qv, learner.last_qmax
+    assert qv_on.shape == qm_on.shape == (B, T, A) and qv_tg.shape == qm_tg.shape == (B, T + 1, A)
+    rows = dict(qv_on=normwise(qv_on, ex["rows_on"][0]), qmax_on=normwise(qm_on, ex["rows_on"][1]),
+                qv_tg=normwise(qv_tg, ex["rows_tg"][0]), qmax_tg=normwise(qm_tg, ex["rows_tg"][1]))
+    print(f"{tag} qplex rows:", {k: f"{v:.2e}" for k, v in rows.items()})
+    assert max(rows.values()) < TOL["fp32"][0], rows
+    return learner, snap, out, info, ex, (cpu, w, g)
+
+
+@pytest.mark.parametrize("A,B,T", SHAPES)
+def test_update_fp32(monkeypatch, A, B, T):
+    require_gpu()
+    from tests.test_gpu_learner_mixers import make_learner as make_flat_learner
+    learner, _, _, _, _, (cpu, w, g) = _update(monkeypatch, f"({A},{B},{T})", A, B, T)
+    # the dispatch took: the agent gradient differs from the QMIX learner's on this batch
+    other, _, _ = make_flat_learner(_cfg_of(A), "qmix")
+    perturb_targets(other)
+    (graw, _, _, _), _ = update(other, to_cuda(cpu), w.cuda())
+    na = learner.na
+    assert other.na == na
+    diff = normwise(g[:na], (graw[:na] / graw[-1]).cpu())
+    print(f"({A},{B},{T}) qplex: agent gradient {diff:.2e} away from the QMIX learner's")
+    assert diff > 1e-3, diff
+
+
+OPTIONS = [("q_lambda", dict(q_lambda=True)), ("rmsprop", dict(optimizer="rmsprop", optim_alpha=0.99, optim_eps=1e-5)),
+           ("noisy", dict(noisy=True)), ("pair", dict(contract="pair")), ("serial", dict(overlap=False))]
+
+
+@pytest.mark.parametrize("name,kw", OPTIONS, ids=[o[0] for o in OPTIONS])
+def test_options(monkeypatch, name, kw):
+    require_gpu()
+    A, B, T = OPT
+    learner, snap, out, info, ex, (cpu, w, g) = _update(monkeypatch, f"{name} ({A},{B},{T})", A, B, T, **kw)
+    if name == "q_lambda":
+        _preconditions(f"{name} qplex {A}", cpu, ex)
+        ek, et = normwise(info["qtot_taken"], ex["qtot_taken"]), normwise(info["qtot_tgt"], ex["qtot_tgt"])
+        print(f"{name} qplex {A}: qtot_taken {ek:.2e} qtot_tgt {et:.2e}")
+        assert ek < TOL["fp32"][0] and et < TOL["fp32"][0], (ek, et)
+    if name == "rmsprop":
+        graw = out[0]
+        ref = rmsprop_ref(snap.params, graw[:-1], snap.v, lr=learner.lr, alpha=0.99, eps=1e-5, weight_decay=0.0,
+                          max_norm=learner.clip, grad_div=float(graw[-1]))
+        es, ep, bar_p = rmsprop_errors(learner.params, learner.exp_avg_sq, ref, snap.params)
+        print(f"rmsprop {A}: square_avg {es:.2e} p {ep:.2e} (bar {bar_p:.2e})")
+        assert es <= 1e-6 and ep <= bar_p, (es, ep, bar_p)
+        assert learner.step_count == 1 and not learner.exp_avg.any()
+    if name == "noisy":
+        assert learner.noisy and float(g[learner.na_net:learner.na].abs().max()) > 0
+
+
+def test_bf16():
+    """A bf16 agent under the fp32 mixer: finite, qtot is the fp64 mixer on the GPU's own rows, bit-reproducible."""
+    require_gpu()
+    A, B, T = OPT
+    learner, pa, pm = make_learner(_cfg_of(A), precision="bf16")
+    perturb_targets(learner)
+    cpu, w = masked_batch(A, B, T, SEED)
+    snap = Snapshot(learner)
+    out, info = update(learner, to_cuda(cpu), w.cuda())
+    assert all(bool(torch.isfinite(x).all()) for x in out)
+    qv, qm = learner.last_qv[0].cpu().double(), learner.last_qmax[0].cpu().double()
+    u = cpu["actions"][:, :T, :, 0]
+    want = qplex_model.qplex_forward(pm, qv, qm, u, cpu["state"][:, :T].reshape(B, T, -1).double(), NA)
+    eq = normwise(info["qtot"], want)
+    share = float((qv != qm).double().mean())
+    print(f"bf16 ({A},{B},{T}) qplex: qtot against the fp64 mixer on last_qv / last_qmax {eq:.2e} (q != m {share:.3f})")
+    assert eq < 1e-5 and share >= NEQ_SHARE, (eq, share)
+    snap.restore()
+    again, _ = update(learner, to_cuda(cpu), w.cuda())
+    assert all(torch.equal(a, b) for a, b in zip(out, again))
+
+
+# ---- checkpoints and state -----------------------------------------------------
+def test_checkpoints_and_state(tmp_path):
+    require_gpu()
+    from tests.test_gpu_learner_masks import make_learner as make_transformer_learner
+    from tests.test_gpu_learner_mixers import make_learner as make_flat_learner
+    A, B, T = OPT
+    cfg = _cfg_of(A)
+    learner, _, pm = make_learner(cfg)
+    cpu, w = masked_batch(A, B, T, SEED)
+    update(learner, to_cuda(cpu), w.cuda())
+    learner.save_models(str(tmp_path))
+    saved = torch.load(os.path.join(tmp_path, "mixer.th"), weights_only=True)
+    assert list(saved) == qplex_model.keys(4)
+    fresh, _, _ = make_learner(cfg)
+    fresh.load_models(str(tmp_path))
+    assert torch.equal(fresh.params, learner.params) and fresh.step_count == learner.step_count == 1
+    assert torch.equal(fresh.exp_avg, learner.exp_avg) and torch.equal(fresh.exp_avg_sq, learner.exp_avg_sq)
+    sd = learner.state_dict()
+    assert sd["mixer"] == "qplex" and sd["nm"] == learner.nm == 73940
+    fresh2, _, _ = make_learner(cfg)
+    fresh2.load_state_dict(sd)
+    assert torch.equal(fresh2.params, learner.params) and torch.equal(fresh2.target_params, learner.target_params)
+    # both continue bit for bit
+    a, _ = update(learner, to_cuda(cpu), w.cuda(), 1)
+    b, _ = update(fresh2, to_cuda(cpu), w.cuda(), 1)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    # another kind's checkpoint or run state is refused, naming both, before anything is overwritten
+    others = [(make_flat_learner(cfg, "qmix")[0], "qmix"), (make_flat_learner(cfg, "vdn")[0], "vdn"),
+              (make_transformer_learner(cfg, model_seed=0)[0], "transformer")]
+    for other, name in others:
+        before = other.params.clone()
+        with pytest.raises(ValueError, match=rf"qplex.*{name}"):
+            other.load_models(str(tmp_path))
+        with pytest.raises(ValueError, match="mixer"):
+            other.load_state_dict(sd)
+        assert torch.equal(other.params, before)
+    # ... and theirs by this one
+    other, name = others[0]
+    os.makedirs(tmp_path / "qmix")
+    other.save_models(str(tmp_path / "qmix"))
+    before = learner.params.clone()
+    with pytest.raises(ValueError, match=r"qmix.*qplex"):
+        learner.load_models(str(tmp_path / "qmix"))
+    with pytest.raises(ValueError, match="mixer"):
+        learner.load_state_dict(other.state_dict())
+    assert torch.equal(learner.params, before)
+
+
+def test_pipeline_option():
+    require_gpu()
+    from t2omca_amd.learner import TDLearner
+    cfg = _cfg_of(16)
+    with pytest.raises(ValueError, match="pipeline=True"):
+        TDLearner(*modules(cfg), pipeline=True)
+    learner = TDLearner(*modules(cfg), pipeline="auto")
+    cpu, w = masked_batch(16, 3, 4, SEED)
+    out, _ = update(learner, to_cuda(cpu), w.cuda())
+    assert all(bool(torch.isfinite(x).all()) for x in out)
+
+
+def test_logging():
+    require_gpu()
+    from t2omca_amd.statlog import StatsLogger
+    log = StatsLogger(out=lambda line: None)
+    learner, _, _ = make_learner(_cfg_of(8), logger=log, learner_log_interval=1)
+    cpu, w = masked_batch(8, 6, 5, SEED)
+    learner.train(to_cuda(cpu), 10, 0, per_weight=w.cuda())
+    torch.cuda.synchronize()
+    recent = log.recent()
+    assert set(recent) >= {"loss_td", "grad_norm", "td_error_abs", "q_taken_mean", "target_mean"}, recent
+    assert all(torch.isfinite(torch.tensor(v)) for v in recent.values()), recent
+
+
+# ---- data parallel ---------------------------------------------------------------
+DP_A, DP_B, DP_T = 8, 6, 5
+
+
+def _dp_learner(seed, device, pg=None):
+    from t2omca_amd.learner import TDLearner
+    return TDLearner(*modules(_cfg_of(DP_A), device=device, seed=seed), process_group=pg, target_update_interval=2)
+
+
+def _dp_batch(device):
+    cpu, w = masked_batch(DP_A, DP_B, DP_T, SEED)
+    cpu["terminated"][1, 3] = 1  # ragged masks: the shards' Σ mask differ
+    cpu["filled"][4, 4:] = 0
+    return {k: v.to(device) for k, v in cpu.items()}, w.to(device)
+
+
+def _dp_worker(rank, world, port, out):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from t2omca_amd.distributed import shard_bounds
+        learner = _dp_learner(100 + rank, dev)  # different init per rank: the broadcast must fix it
+        batch, w = _dp_batch(dev)
+        lo, hi = shard_bounds(DP_B, rank, world)
+        learner.train({k: v[lo:hi] for k, v in batch.items()}, 0, 0, per_weight=w[lo:hi])
+        torch.cuda.synchronize()
+        out.put((rank, torch.stack([learner.params, learner.grad[:-1] / learner.grad[-1]]).cpu().numpy()))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_dp_two_ranks_qplex():
+    """Two gloo ranks on one device equal the full-batch update from the same state."""
+    require_gpu()
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    try:
+        res = dict(q.get(timeout=240) for _ in procs)
+    finally:
+        for p in procs:
+            p.join(timeout=60)
+    for p in procs:
+        assert p.exitcode == 0
+    r0, r1 = torch.from_numpy(res[0]), torch.from_numpy(res[1])
+    assert torch.equal(r0, r1)
+    dev = torch.device("cuda", 0)
+    full = _dp_learner(100, dev)
+    batch, w = _dp_batch(dev)
+    full.train(batch, 0, 0, per_weight=w)
+    torch.cuda.synchronize()
+    gerr = normwise(r0[1], (full.grad[:-1] / full.grad[-1]).cpu())
+    err = normwise(r0[0], full.params.cpu())
+    print(f"dp qplex: grad {gerr:.2e}, params {err:.2e}")
+    assert gerr < 1e-6 and err < 1e-6, (gerr, err)

@@ -1,7 +1,7 @@
-"""Time TDLearner.train with the transformer, QMIX and VDN mixers.
+"""Time TDLearner.train with the transformer, QMIX, VDN and QPLEX (dmaq) mixers.
 
     python tools/time_mixers.py [--shapes headline,reference-bf16,reference-fp32]
-                                [--kinds transformer,qmix,vdn] [--updates 20] [--warmup 5]
+                                [--kinds transformer,qmix,vdn[,dmaq]] [--updates 20] [--warmup 5]
 
 Device events around each update, warm-up first, the variants alternating in one
 process (every variant sees the same clocks and the same neighbours), medians printed
@@ -38,7 +38,8 @@ def learner_of(kind, A, precision):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=",".join(SHAPES))
-    ap.add_argument("--kinds", default="transformer,qmix,vdn")
+    ap.add_argument("--kinds", default="transformer,qmix,vdn",
+                    help="comma-separated args.mixer names: transformer, qmix, vdn, dmaq (= qplex)")
     ap.add_argument("--updates", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     a = ap.parse_args()
@@ -63,6 +64,9 @@ def main():
                "min_ms": {k: round(min(v), 4) for k, v in ms.items()}}
         if "qmix" in ms and "transformer" in ms:
             out["qmix_faster_than_transformer"] = out["median_ms"]["qmix"] < out["median_ms"]["transformer"]
+        for k in ("dmaq", "qplex"):
+            if k in ms and "transformer" in ms:
+                out[k + "_faster_than_transformer"] = out["median_ms"][k] < out["median_ms"]["transformer"]
         print(json.dumps(out), flush=True)
         del learners, batch
         torch.cuda.empty_cache()
