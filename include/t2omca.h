@@ -207,6 +207,9 @@ int t2o_unpack_grads(const t2o_layout* L, const float* params, const float* gpac
 #define T2O_ARGS_QPLEX_SELECT 17
 #define T2O_ARGS_QPLEX_FWD 18
 #define T2O_ARGS_QPLEX_BWD 19
+/* (20 stays unassigned too: published as unknown while 19 was the last id) */
+#define T2O_ARGS_RNN_FWD 21
+#define T2O_ARGS_RNN_BWD 22
 int t2o_args_sizeof(int which); /* sizeof the T2O_ARGS_* struct, -1 for an unknown one */
 
 /* Agent unroll forward (TransformerAgent.forward over t, transf_agent.py:54-76) for
@@ -816,6 +819,90 @@ typedef struct {
 int t2o_qplex_bwd(const t2o_qplex_bwd_args* a, void* stream);
 int t2o_qplex_bwd_slabs(int B, int T);                       /* T2O_EINVAL on a bad size */
 int64_t t2o_qplex_bwd_work_floats(int B, int T, int A, int H, int HA, int K);
+
+/* ---- the GRU agent of the QMIX baselines (t2o_rnn.hip; agent: rnn).  No agent but the
+ * transformer ships with the reference: the DECLARED definition after PyMARL2's
+ * modules/agents/n_rnn_agent.RNNAgent with use_layer_norm = False (parity-unpinned,
+ * DESIGN.md §5).  Per agent row and step, gates in torch.nn.GRUCell's order r, z, n:
+ *   x  = relu(fc1 in + b1)
+ *   r  = sigmoid(W_ir x + b_ir + W_hr h + b_hr)    z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
+ *   n  = tanh(W_in x + b_in + r * (W_hn h + b_hn))
+ *   h' = (1 - z) * n + z * h                       q = fc2 h' + b2
+ * in = [obs ; onehot(action at t-1) if last_action ; onehot(agent) if agent_id]
+ * (BasicMAC._build_inputs), IN = OBS + NA·[last_action] + A·[agent_id]; it is never
+ * written to memory.  Parameters are read straight from a flat buffer in the
+ * registration order fc1.weight [H][IN], fc1.bias, rnn.weight_ih [3H][H], rnn.weight_hh,
+ * rnn.bias_ih, rnn.bias_hh, fc2.weight [NA][H], fc2.bias: t2o_rnn_param_count floats.
+ * All arithmetic is fp32.  Limits: 1 <= A <= 64, 1 <= OBS and IN <= 656, 1 <= NA <= 16, H in
+ * {32, 64}, B·T1·A < 2^27.  (Added within ABI 6: nothing existing moved.)
+ * T2O_EINVAL for a null required pointer, a bad size or a misaligned buffer, before
+ * any launch; no allocation, no synchronisation, no atomics. */
+int64_t t2o_rnn_param_count(int IN, int H, int NA); /* T2O_EINVAL on a size outside the limits */
+
+/* GRU agent forward of up to two networks sharing the inputs, over steps t0 <= t < t1
+ * of T1 from h0 (the state before step t0; NULL: zeros).  The one-hot of the last
+ * action at step t reads actions[b][t - 1 + act_shift] and is zero where that step is
+ * negative or actions is NULL (act_shift 0: a whole episode; 1: one rollout step whose
+ * actions hold the previous step's).  The float buffers are 16-byte aligned. */
+typedef struct {
+  const float* params_on;
+  const float* params_tg;     /* NULL: one network */
+  const float* obs;           /* [b][t][a][OBS], element strides obs_sb, obs_st; [a][OBS] dense */
+  int64_t obs_sb, obs_st;
+  const int64_t* actions;     /* [b][t][a], strides act_sb, act_st, or NULL */
+  int64_t act_sb, act_st;
+  const float* h0_on;         /* [b][a][H], episode stride h0_sb (a multiple of 4), or NULL */
+  const float* h0_tg;
+  int64_t h0_sb;
+  float* x_on;                /* out [B][T1][A][H]: relu(fc1), for the backward; or NULL */
+  float* gi_on;               /* out [B][T1][A][3H]: W_ih x + b_ih */
+  float* gi_tg;
+  float* q_on;                /* out [B][T1][A][NA] */
+  float* h_on;                /* out [B][T1][A][H] */
+  float* q_tg;
+  float* h_tg;
+  int32_t B, T1, A, OBS, NA, H;
+  int32_t last_action, agent_id, act_shift;
+  int32_t t0, t1;
+  int32_t reserved_;
+} t2o_rnn_fwd_args;
+int t2o_rnn_fwd(const t2o_rnn_fwd_args* a, void* stream);
+
+/* GRU agent backward of one network over steps t < T of a forward whose buffers have
+ * Ts >= T steps.  dL/dq enters either as gchosen [B][T][A], the gradient at
+ * actions[b][t][a] (the learner's form), or as gq [B][T][A][NA]: exactly one of them.
+ * gh (optional) adds dL/dh[b][t][a][:].  The gates are recomputed from gi, h and W_hh.
+ * The weight gradients leave as t2o_rnn_bwd_slabs(B, T, A) partial slabs
+ * [nslab][t2o_rnn_param_count] in the parameter order, each element written once by
+ * one workgroup in a fixed order (sum them with t2o_reduce_slabs).  work:
+ * t2o_rnn_bwd_work_floats floats (per row the gradients of gi, of gh's n gate and of
+ * fc1's pre-activation). */
+typedef struct {
+  const float* params;
+  const float* obs;
+  int64_t obs_sb, obs_st;
+  const int64_t* actions;     /* [b][t][a], strides act_sb, act_st (gchosen, last_action) or NULL */
+  int64_t act_sb, act_st;
+  const float* h0;            /* [b][a][H], episode stride h0_sb, or NULL: zeros */
+  int64_t h0_sb;
+  const float* x;             /* the forward's x_on, gi_on, h_on */
+  const float* gi;
+  const float* h;
+  const float* gchosen;       /* [B][T][A] or NULL */
+  const float* gq;            /* [B][T][A][NA] or NULL */
+  const float* gh;            /* [B][T][A][H] or NULL */
+  float* gh0;                 /* out [B][A][H] or NULL */
+  float* gslabs;              /* out [>= t2o_rnn_bwd_slabs][t2o_rnn_param_count] */
+  float* work;                /* t2o_rnn_bwd_work_floats floats, 16-byte aligned */
+  int64_t work_floats;
+  int32_t max_slabs;
+  int32_t B, T, Ts, A, OBS, NA, H;
+  int32_t last_action, agent_id, act_shift;
+  int32_t reserved_;
+} t2o_rnn_bwd_args;
+int t2o_rnn_bwd(const t2o_rnn_bwd_args* a, void* stream);
+int t2o_rnn_bwd_slabs(int B, int T, int A);                  /* T2O_EINVAL on a bad size */
+int64_t t2o_rnn_bwd_work_floats(int B, int T, int A, int H);
 
 /* Diagnostic: runs the cross-lane primitives the kernels rely on (4-lane
  * all-reduces via ds_bpermute and via gfx950 permlane swaps, 16-lane DPP row

@@ -107,9 +107,16 @@ QplexFwdArgs = _args_class("QplexFwdArgs", 18, """params_on:P, params_tg:P, stat
 QplexBwdArgs = _args_class("QplexBwdArgs", 19, """params:P, states:P, st_sb:J, st_st:J, qv:P, qmax:P, act:P, gy:P,
     gqv:P, gslabs:P, work:P, work_floats:J, max_slabs:I, phase:I, parts:I, B:I, T:I, A:I, S:I, NA:I, H:I, HA:I,
     K:I""")
+# (id 20 stays unassigned too: t2o_args_sizeof(20) is published as -1)
+RnnFwdArgs = _args_class("RnnFwdArgs", 21, """params_on:P, params_tg:P, obs:P, obs_sb:J, obs_st:J, actions:P, act_sb:J,
+    act_st:J, h0_on:P, h0_tg:P, h0_sb:J, x_on:P, gi_on:P, gi_tg:P, q_on:P, h_on:P, q_tg:P, h_tg:P, B:I, T1:I, A:I, OBS:I,
+    NA:I, H:I, last_action:I, agent_id:I, act_shift:I, t0:I, t1:I, reserved_:I""")
+RnnBwdArgs = _args_class("RnnBwdArgs", 22, """params:P, obs:P, obs_sb:J, obs_st:J, actions:P, act_sb:J, act_st:J, h0:P,
+    h0_sb:J, x:P, gi:P, h:P, gchosen:P, gq:P, gh:P, gh0:P, gslabs:P, work:P, work_floats:J, max_slabs:I, B:I, T:I, Ts:I,
+    A:I, OBS:I, NA:I, H:I, last_action:I, agent_id:I, act_shift:I, reserved_:I""")
 ARGS_STRUCTS = (AgentFwdArgs, AgentBwdArgs, MixerFwdArgs, MixerBwdArgs, TapeArgs, TDArgs, TDStatsArgs, TDQLambdaArgs,
                 NoiseArgs, NoisyFwdArgs, NoisyBwdArgs, NoisyWgradArgs, QSelectArgs, QmixFwdArgs, QmixBwdArgs,
-                QplexSelectArgs, QplexFwdArgs, QplexBwdArgs)
+                QplexSelectArgs, QplexFwdArgs, QplexBwdArgs, RnnFwdArgs, RnnBwdArgs)
 NOISE_KINDS = {"learner_online": 0, "learner_target": 1, "runner": 2, "module": 3}  # include/t2omca.h T2O_NOISE_*
 EP_STATS = 10  # include/t2omca.h T2O_EP_STATS
 
@@ -175,6 +182,11 @@ EXPORTS = {
     "t2o_qplex_bwd": (ctypes.c_int, [ctypes.POINTER(QplexBwdArgs), ctypes.c_void_p]),
     "t2o_qplex_bwd_slabs": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "t2o_qplex_bwd_work_floats": (ctypes.c_int64, [ctypes.c_int] * 6),
+    "t2o_rnn_param_count": (ctypes.c_int64, [ctypes.c_int] * 3),
+    "t2o_rnn_fwd": (ctypes.c_int, [ctypes.POINTER(RnnFwdArgs), ctypes.c_void_p]),
+    "t2o_rnn_bwd": (ctypes.c_int, [ctypes.POINTER(RnnBwdArgs), ctypes.c_void_p]),
+    "t2o_rnn_bwd_slabs": (ctypes.c_int, [ctypes.c_int] * 3),
+    "t2o_rnn_bwd_work_floats": (ctypes.c_int64, [ctypes.c_int] * 4),
     "t2o_probe_lane_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_scatter_ops": (ctypes.c_int, [ctypes.c_void_p] * 3),
     "t2o_probe_xdl_hazards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -217,13 +229,17 @@ _OPTIONAL = _DIAGNOSTIC | {"t2o_td_stats", "t2o_episode_stats", "t2o_td_qlambda"
                            "t2o_qmix_bwd_slabs", "t2o_qmix_bwd_work_floats", "t2o_vdn_bwd",
                            # ... and the QPLEX mixer
                            "t2o_qplex_param_count", "t2o_qplex_select", "t2o_qplex_fwd", "t2o_qplex_bwd",
-                           "t2o_qplex_bwd_slabs", "t2o_qplex_bwd_work_floats"}
+                           "t2o_qplex_bwd_slabs", "t2o_qplex_bwd_work_floats",
+                           # ... and the GRU agent
+                           "t2o_rnn_param_count", "t2o_rnn_fwd", "t2o_rnn_bwd", "t2o_rnn_bwd_slabs",
+                           "t2o_rnn_bwd_work_floats"}
 # argument structs of optional exports: no size to check where the export is absent
 _STRUCT_EXPORT = {TDStatsArgs: "t2o_td_stats", TDQLambdaArgs: "t2o_td_qlambda", NoiseArgs: "t2o_noise_normal",
                   NoisyFwdArgs: "t2o_noisy_head_fwd", NoisyBwdArgs: "t2o_noisy_head_bwd",
                   NoisyWgradArgs: "t2o_noisy_head_wgrad", QSelectArgs: "t2o_q_select",
                   QmixFwdArgs: "t2o_qmix_fwd", QmixBwdArgs: "t2o_qmix_bwd",
-                  QplexSelectArgs: "t2o_qplex_select", QplexFwdArgs: "t2o_qplex_fwd", QplexBwdArgs: "t2o_qplex_bwd"}
+                  QplexSelectArgs: "t2o_qplex_select", QplexFwdArgs: "t2o_qplex_fwd", QplexBwdArgs: "t2o_qplex_bwd",
+                  RnnFwdArgs: "t2o_rnn_fwd", RnnBwdArgs: "t2o_rnn_bwd"}
 
 _lib = None
 

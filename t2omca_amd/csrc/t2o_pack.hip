@@ -356,6 +356,8 @@ extern "C" int t2o_args_sizeof(int which) {
     case T2O_ARGS_QPLEX_SELECT: return (int)sizeof(t2o_qplex_select_args);
     case T2O_ARGS_QPLEX_FWD: return (int)sizeof(t2o_qplex_fwd_args);
     case T2O_ARGS_QPLEX_BWD: return (int)sizeof(t2o_qplex_bwd_args);
+    case T2O_ARGS_RNN_FWD: return (int)sizeof(t2o_rnn_fwd_args);
+    case T2O_ARGS_RNN_BWD: return (int)sizeof(t2o_rnn_bwd_args);
     default: return -1;
   }
 }

@@ -75,6 +75,18 @@ its dmaq_qatten_learner and double_q) is the third of these flat 
   dL/dq_chosen = dL/dy · w, the rows' activations           t2o_qplex_bwd phase 1
   weight-gradient slabs, their sum, the all-reduce          t2o_qplex_bwd phase 2, t2o_reduce_slabs: side stream
 No gradient reaches the maxima; ``learner.last_qmax`` keeps them beside ``last_qv``.
+
+A GRU agent (modules.RNNAgent, ``agent.kind`` "rnn", PyMARL2's agent: rnn)
+under one of the flat mixers replaces the agent's launches — a transformer-agent learner
+launches exactly the above:
+
+  both networks' fc1, ReLU and W_ih products over every    t2o_rnn_fwd (two launches: the
+      (episode, step, agent) row, then the recurrence       time-parallel rows, the recurrence)
+  the reverse recurrence from dL/dq_chosen, the rows'      t2o_rnn_bwd (three launches),
+      dL/dx, the weight-gradient slabs and their sum        t2o_reduce_slabs
+It reads its parameters straight from the flat buffers (no pack), builds its inputs
+(observation, last action's one-hot, agent's one-hot) inside the kernels, and is fp32 in
+both precisions.  A transformer mixer, pipeline=True and a noisy head are ValueErrors.
 """
 import dataclasses
 import os
@@ -90,6 +102,16 @@ from .state import check_fields, copy_checked
 
 OPTIMIZERS = {"adam": "Adam", "rmsprop": "RMSprop"}  # TDLearner(optimizer=...): the torch.optim class of opt.th
 MIXERS = ("transformer", "qmix", "vdn", "qplex")  # modules.TransformerMixer / QMixer / VDNMixer / QPlexMixer .kind
+AGENTS = ("transformer", "rnn")  # modules.TransformerAgent / RNNAgent .kind
+
+
+def _agent_kind_of(state_dict):
+    """Which of AGENTS wrote this agent.th (None: neither), by its keys."""
+    if "rnn.weight_hh" in state_dict and "fc1.weight" in state_dict:
+        return "rnn"
+    if any(k.startswith("transformer.tblocks") for k in state_dict):
+        return "transformer"
+    return None
 
 
 def _mixer_kind_of(state_dict):
@@ -163,6 +185,20 @@ class TDLearner:
         if pipeline is True and self.mixer_kind != "transformer":
             raise ValueError(f"pipeline=True runs the update in step ranges, which needs the decoupled transformer "
                              f"mixer; a {self.mixer_kind} mixer runs the sequential update (pipeline='auto' or False)")
+        # which agent (modules.*.kind): the reference's TransformerAgent, or the declared GRU agent
+        self.agent_kind = getattr(agent, "kind", "transformer")
+        if self.agent_kind not in AGENTS:
+            raise ValueError(f"agent.kind must be one of {list(AGENTS)}, got {self.agent_kind!r}")
+        if self.agent_kind == "rnn":
+            if self.mixer_kind == "transformer":
+                raise ValueError("an rnn agent trains under the flat mixers (qmix, vdn, qplex) that are supported; "
+                                 "the transformer mixer reads the transformer agent's hidden tokens")
+            if pipeline is True:
+                raise ValueError("pipeline=True runs the update in step ranges, which the rnn agent's kernels do "
+                                 "not take (pipeline='auto' or False)")
+            if getattr(getattr(agent, "args", None), "action_selector", None) == "noisy-new":
+                raise ValueError("an rnn agent has no noisy head (action_selector='noisy-new' needs the "
+                                 "transformer agent)")
         dev = next(agent.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("TDLearner needs the modules on a HIP device (no CPU fallback)")
@@ -172,7 +208,8 @@ class TDLearner:
         # and the Adam master weights stay fp32
         prec = 1 if precision == "bf16" else 0
         self.precision = precision
-        self.sa = dataclasses.replace(agent.shape, prec=prec)
+        # (the GRU agent's ops.RnnShape: fp32 in both precisions)
+        self.sa = agent.shape if self.agent_kind == "rnn" else dataclasses.replace(agent.shape, prec=prec)
         if self.mixer_kind == "transformer":
             self.sm = dataclasses.replace(mixer.shape, prec=prec)
         else:  # ops.QmixShape / QplexShape (fp32 in both precisions), or None: VDN has no parameters
@@ -225,8 +262,9 @@ class TDLearner:
         self.step_count = 0
         self.last_target_update_episode = 0
         self.timer = None   # optional callable(tag) recording HIP events around the big kernels
-        self.pack_a = torch.empty(self.sa.layout().pack_floats, device=dev)
-        self.pack_at = torch.empty_like(self.pack_a)
+        if self.agent_kind != "rnn":  # (the GRU agent reads the flat parameters: no pack)
+            self.pack_a = torch.empty(self.sa.layout().pack_floats, device=dev)
+            self.pack_at = torch.empty_like(self.pack_a)
         if self.mixer_kind == "transformer":  # (the other mixers read the flat parameters: no pack)
             self.pack_m = torch.empty(self.sm.layout().pack_floats, device=dev)
             self.pack_mt = torch.empty_like(self.pack_m)
@@ -280,7 +318,8 @@ class TDLearner:
         return self.last_noise
 
     def _pack_targets(self):
-        ops.pack_params(self.sa, self.target_params[:self.na_net], self.pack_at)
+        if self.agent_kind != "rnn":
+            ops.pack_params(self.sa, self.target_params[:self.na_net], self.pack_at)
         if self.mixer_kind == "transformer":
             ops.pack_params(self.sm, self.target_params[self.na:], self.pack_mt)
 
@@ -358,7 +397,7 @@ class TDLearner:
         agent.th and the target mixer is left as it is; opt.th is optional, and one
         written by the other optimiser is a ValueError naming both, and so is a mixer.th
         of another kind of mixer (told by its keys: transformer, qmix, qplex, or vdn's empty
-        dict).  opt.th follows the
+        dict), and an agent.th of the other kind of agent (transformer or rnn).  opt.th follows the
         modules' parameter order (a noisy agent: q_basic.u_w, u_b, s_w, s_b last of the
         agent's); an agent.th of the other head, or an opt.th whose per-parameter shapes
         are not these modules', is a ValueError that says so.  Every check comes before
@@ -371,6 +410,9 @@ class TDLearner:
             raise ValueError(f"opt.th holds the state of a {OPTIMIZERS[held]} optimiser, this learner runs "
                              f"{OPTIMIZERS[self.optimizer]} (optimizer={self.optimizer!r})")
         agent_sd = load("agent.th")
+        if _agent_kind_of(agent_sd) != self.agent_kind:
+            raise ValueError(f"agent.th holds a {_agent_kind_of(agent_sd)} agent, this learner's agent is a "
+                             f"{self.agent_kind} one (the kinds are {' and '.join(AGENTS)})")
         if ("q_basic.u_w" in agent_sd) != self.noisy:
             kinds = ("a NoisyLinear (noisy-new)", "a plain Linear")
             raise ValueError(f"agent.th holds {kinds['q_basic.u_w' not in agent_sd]} q_basic head, this learner's "
@@ -436,7 +478,9 @@ class TDLearner:
                 # noise_seed and step_count alone, so no further state
                 "noisy": self.noisy, "noise_seed": self.noise_seed,
                 # the kind of mixer (MIXERS) the mixer half of the flat buffers belongs to
-                "mixer": self.mixer_kind}
+                "mixer": self.mixer_kind,
+                # the kind of agent (AGENTS) the agent half belongs to
+                "agent": self.agent_kind}
 
     def load_state_dict(self, sd):
         """In place into the flat buffers, which the modules' parameters view; then
@@ -446,13 +490,14 @@ class TDLearner:
         (q_lambda) or the optimiser differ; a state saved before the last three
         existed holds their defaults.  Likewise `noisy` (a state saved before it
         existed is a plain agent's), and with a noisy agent `noise_seed`; and `mixer`, the
-        kind of mixer (a state saved before it existed is a transformer mixer's)."""
+        kind of mixer (a state saved before it existed is a transformer mixer's); and
+        `agent`, the kind of agent (a state saved before it existed is a transformer agent's)."""
         sd = {"q_lambda": False, "optimizer": "adam", "optim_alpha": 0.99, "noisy": False, "noise_seed": 0,
-              "mixer": "transformer", **sd}
+              "mixer": "transformer", "agent": "transformer", **sd}
         sd["optim_alpha"] = float(sd["optim_alpha"])
         # (noisy before na: a noisy state in a plain learner is told by its name, not by its size)
         head = {"noisy": self.noisy, **({"noise_seed": self.noise_seed} if self.noisy else {})}
-        check_fields("TDLearner", sd, {"format": 1, "mixer": self.mixer_kind, **head, "na": self.na, "nm": self.nm, "precision": self.precision,
+        check_fields("TDLearner", sd, {"format": 1, "agent": self.agent_kind, "mixer": self.mixer_kind, **head, "na": self.na, "nm": self.nm, "precision": self.precision,
                                        "q_lambda": self.q_lambda, "optimizer": self.optimizer,
                                        "optim_alpha": self.alpha})
         with torch.no_grad():
@@ -703,7 +748,9 @@ class TDLearner:
         loss, the agent BPTT, the optimiser step and the statistics are the transformer
         path's; steps 2 and 4 are the select kernel and the flat mixers' kernels.  The
         mixers read the state alone, so gh is None: no gradient reaches the agents'
-        hidden states from them and detach_mixer_hidden has no effect."""
+        hidden states from them and detach_mixer_hidden has no effect.  With a GRU agent
+        (agent.kind "rnn") steps 1 and 5 are its kernels; contract and detach_mixer_hidden
+        have no effect on them (no tape to contract, no gradient into the hidden states)."""
         B, T1, A, _ = obs.shape
         T = T1 - 1
         dev = self.device
@@ -719,11 +766,21 @@ class TDLearner:
                 noise_drawn = side.record_event()
             self.grad.zero_()
             grad_clear = side.record_event()
-        ops.pack_params(self.sa, self.params[:self.na_net], self.pack_a)
-        hmid = self._buf("hmid", (B, T1, self.sa.D - 1, A, self.sa.E)) if self.sa.D > 1 else None
+        rnn = self.agent_kind == "rnn"
         # 1. agents: online + target over t = 0..T
-        q_on, h_on, q_tg, h_tg = ops.agent_unroll_fwd(self.sa, self.pack_a, obs, pack_tg=self.pack_at,
-                                                      timer=self.timer, hmid_on=hmid)
+        if rnn:
+            H, NA = self.sa.H, self.sa.NA
+            fwd = {k: self._buf("rnn_" + k, (B, T1, A, n)) for k, n in
+                   (("q_on", NA), ("h_on", H), ("gi_on", 3 * H), ("x_on", H), ("q_tg", NA), ("h_tg", H),
+                    ("gi_tg", 3 * H))}
+            ops.rnn_agent_fwd(self.sa, self.params[:self.na], obs, actions=act,
+                              params_tg=self.target_params[:self.na], outs=fwd, timer=self.timer)
+            q_on, h_on, q_tg, h_tg = fwd["q_on"], fwd["h_on"], fwd["q_tg"], fwd["h_tg"]
+        else:
+            ops.pack_params(self.sa, self.params[:self.na_net], self.pack_a)
+            hmid = self._buf("hmid", (B, T1, self.sa.D - 1, A, self.sa.E)) if self.sa.D > 1 else None
+            q_on, h_on, q_tg, h_tg = ops.agent_unroll_fwd(self.sa, self.pack_a, obs, pack_tg=self.pack_at,
+                                                          timer=self.timer, hmid_on=hmid)
         if self.noisy:
             main.wait_event(noise_drawn)
             self._head_fwd(q_on, h_on, q_tg, h_tg, eps_on, eps_tg)
@@ -786,8 +843,12 @@ class TDLearner:
         if self.noisy:  # dL/dh = dL/dq_chosen · W_t[action]; the agent BPTT then takes no q gradient
             gh, gpart = self._head_bwd(gqv, act, h_on, eps_on, None)
             gchosen = None
-        tape_a = self._slab("tape_a", ops.tape_floats(self.sa, ops.agent_tape_tiles(B, T, A)))
-        slabs_a = self._slab("a", ops.agent_slab_count(B, A) * self.sa.layout().grad_total)
+        if rnn:
+            slabs_a = self._slab("rnn", ops.rnn_slab_count(B, T, A) * self.na)
+            work_a_ = self._slab("rnn_work", ops.rnn_work_floats(self.sa, B, T))
+        else:
+            tape_a = self._slab("tape_a", ops.tape_floats(self.sa, ops.agent_tape_tiles(B, T, A)))
+            slabs_a = self._slab("a", ops.agent_slab_count(B, A) * self.sa.layout().grad_total)
 
         def mixer_grads():
             if mixer_dw is not None:
@@ -796,6 +857,11 @@ class TDLearner:
 
         def agent_grads():
             # 5. agent BPTT, its gradients in the reference parameter order
+            if rnn:
+                _, nslab_a, _ = ops.rnn_agent_bwd(self.sa, self.params[:self.na], obs, fwd, T=T, actions=act,
+                                                  gchosen=gchosen, slabs=slabs_a, work=work_a_, timer=self.timer)
+                ops.reduce_slabs(slabs_a, nslab_a, self.grad[:self.na])
+                return
             ga, _ = ops.agent_unroll_bwd(self.sa, self.pack_a, obs, h_on, gchosen=gchosen, actions=act, gh=gh,
                                          slabs=slabs_a, timer=self.timer, hmid=hmid, tape=tape_a)
             ops.unpack_grads(self.sa, self.params[:self.na_net], ga, self.grad[:self.na_net])

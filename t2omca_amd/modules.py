@@ -214,6 +214,8 @@ class TransformerAgent(nn.Module):
     "module", counter ``noise_calls``, which it increments) and runs the head on the
     noisy-head kernels; an eval-mode forward is the mean head, the fused path."""
 
+    kind = "transformer"
+
     def __init__(self, input_shape, args):
         super().__init__()
         self.args = args
@@ -251,6 +253,101 @@ class TransformerAgent(nn.Module):
             self.noise_calls += 1
             q = _NoisyHead.apply(h, nl.u_w, nl.u_b, nl.s_w, nl.s_b, eps_w, eps_b)
         return q.view(b, a, -1), h.view(b, a, -1)
+
+
+class _RnnStep(torch.autograd.Function):
+    """One GRU agent step on the HIP kernels (t2o_rnn_fwd / t2o_rnn_bwd with one step):
+    the parameters enter as separate inputs, their gradients leave as views of one flat
+    buffer (the slab sum, in the parameter order).  `inputs` is the built input row, so
+    the kernels see it as an observation without one-hots."""
+
+    @staticmethod
+    def forward(ctx, shape, inputs, hidden, *params):
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1) for p in params])
+        b, a, nf = inputs.shape
+        obs = inputs.detach().contiguous().view(b, 1, a, nf)
+        h0 = hidden.detach().reshape(b, a, shape.H).contiguous()
+        fwd = ops.rnn_agent_fwd(shape, flat, obs, h0_on=h0)
+        ctx.save_for_backward(flat, obs, h0, fwd["x_on"], fwd["gi_on"], fwd["h_on"])
+        ctx.shape, ctx.param_shapes = shape, [p.shape for p in params]
+        return fwd["q_on"][:, 0], fwd["h_on"][:, 0]
+
+    @staticmethod
+    def backward(ctx, gq, gh):
+        flat, obs, h0, x, gi, h = ctx.saved_tensors
+        shape = ctx.shape
+        b, _, a, _ = obs.shape
+        gq = (gq if gq is not None else torch.zeros(b, a, shape.NA, device=obs.device)).contiguous()
+        gh = None if gh is None else gh.contiguous().view(b, 1, a, shape.H)
+        slabs, nslab, gh0 = ops.rnn_agent_bwd(shape, flat, obs, dict(x_on=x, gi_on=gi, h_on=h), h0=h0,
+                                              gq=gq.view(b, 1, a, shape.NA), gh=gh, want_gh0=True)
+        gflat = ops.reduce_slabs(slabs, nslab, torch.empty_like(flat))
+        return (None, None, gh0) + _split_like(gflat, ctx.param_shapes)
+
+
+class RNNAgent(nn.Module):
+    """The recurrent agent of the QMIX baselines, PyMARL2's modules/agents/n_rnn_agent.py
+    `RNNAgent` with use_layer_norm=False: fc1 -> ReLU -> GRUCell -> fc2, shared by all
+    agents.  No agent but the transformer ships with the reference: this is the DECLARED
+    definition of DESIGN.md §5, parity-unpinned.
+
+    ``input_shape`` is the width of the built input (BasicMAC._build_inputs): the
+    flattened observation, then the one-hot of the last action if args.obs_last_action
+    (default True), then the one-hot of the agent if args.obs_agent_id (default True).
+    H = args.rnn_hidden_dim (64).  Torch's default initialisation; args.use_orthogonal
+    applies orthogonal_init_ to fc1 and fc2 as PyMARL2 does.  ``forward`` takes the built
+    inputs [b, a, input_shape]; ``shape`` describes how the learner and the runner build
+    them from observations and actions inside the kernels."""
+
+    kind = "rnn"
+
+    def __init__(self, input_shape, args):
+        super().__init__()
+        self.args = args
+        self.n_agents = A = int(args.n_agents)
+        self.n_actions = NA = int(args.n_actions)
+        self.hidden_dim = H = int(getattr(args, "rnn_hidden_dim", 64))
+        self.input_shape = IN = int(input_shape)
+        self.obs_last_action = bool(getattr(args, "obs_last_action", True))
+        self.obs_agent_id = bool(getattr(args, "obs_agent_id", True))
+        if getattr(args, "use_layer_norm", False):
+            raise ValueError("RNNAgent: use_layer_norm=True is not supported (the GRU kernels have no LayerNorm)")
+        if H not in ops.RNN_HIDDEN:
+            raise ValueError(f"RNNAgent: rnn_hidden_dim={H}: the GRU kernels take {ops.RNN_LIMITS}")
+        obs_dim = IN - (NA if self.obs_last_action else 0) - (A if self.obs_agent_id else 0)
+        if not (1 <= A <= 64 and 1 <= NA <= 16 and obs_dim >= 1 and IN <= 656):
+            raise ValueError(f"RNNAgent: n_agents={A}, n_actions={NA}, input width {IN} (obs width {obs_dim}): the "
+                             f"GRU kernels take {ops.RNN_LIMITS}")
+        self.fc1 = nn.Linear(IN, H)
+        self.rnn = nn.GRUCell(H, H)
+        self.fc2 = nn.Linear(H, NA)
+        if getattr(args, "use_orthogonal", False):
+            orthogonal_init_(self.fc1)
+            orthogonal_init_(self.fc2, gain=getattr(args, "gain", 0.01))
+        self.shape = ops.RnnShape(A, obs_dim, NA, H, self.obs_last_action, self.obs_agent_id)
+        self._step_shape = ops.RnnShape(A, IN, NA, H, False, False)  # forward's rows are built inputs
+
+    def init_hidden(self):
+        return torch.zeros(1, self.hidden_dim, device=self.args.device)
+
+    def forward(self, inputs, hidden_state):
+        if not inputs.is_cuda:
+            raise RuntimeError("RNNAgent.forward needs HIP-device tensors (no CPU fallback)")
+        b, a, _ = inputs.size()
+        if b * a * self.hidden_dim != hidden_state.numel():
+            hidden_state = hidden_state.expand(b, a, self.hidden_dim)
+        q, h = _RnnStep.apply(self._step_shape, inputs, hidden_state.reshape(b, a, self.hidden_dim),
+                              *self.parameters())
+        return q.view(b, a, -1), h.view(b, a, -1)
+
+
+def make_agent(input_shape, args):
+    """args.agent: "rnn" or "n_rnn" (PyMARL2's name) -> RNNAgent, absent or anything else
+    -> the reference's TransformerAgent."""
+    if getattr(args, "agent", None) in ("rnn", "n_rnn"):
+        return RNNAgent(input_shape, args)
+    return TransformerAgent(input_shape, args)
 
 
 class _MixerStep(torch.autograd.Function):

@@ -1230,3 +1230,205 @@ def qplex_bwd(shape: QplexShape, params, states, qv, qmax, act, gy, *, parts=3, 
         return go, gqv, slabs, nslab
     go(0)
     return gqv, slabs, nslab
+
+
+# ---- the GRU agent of the QMIX baselines (include/t2omca.h t2o_rnn_*) ----
+
+RNN_HIDDEN = (32, 64)
+RNN_LIMITS = "1 <= n_agents <= 64, 1 <= input width <= 656, 1 <= n_actions <= 16, rnn_hidden_dim in {32, 64}"
+
+
+@dataclass(frozen=True)
+class RnnShape:
+    """Sizes of an RNNAgent (modules.RNNAgent): agents, the flattened observation's
+    width, actions, rnn_hidden_dim H, and which one-hots the input carries."""
+    A: int
+    OBS: int
+    NA: int
+    H: int = 64
+    last_action: bool = True
+    agent_id: bool = True
+
+    @property
+    def IN(self):
+        return self.OBS + (self.NA if self.last_action else 0) + (self.A if self.agent_id else 0)
+
+    @property
+    def E(self):
+        """The hidden state's width (what NetShape calls E)."""
+        return self.H
+
+    @property
+    def n_params(self):
+        return int(lib().t2o_rnn_param_count(self.IN, self.H, self.NA))
+
+    @property
+    def agents(self):
+        return self.A
+
+
+def rnn_param_blocks(IN, H, NA):
+    """(state_dict key, shape) of an RNNAgent's parameters in their flat order."""
+    return [("fc1.weight", (H, IN)), ("fc1.bias", (H,)), ("rnn.weight_ih", (3 * H, H)), ("rnn.weight_hh", (3 * H, H)),
+            ("rnn.bias_ih", (3 * H,)), ("rnn.bias_hh", (3 * H,)), ("fc2.weight", (NA, H)), ("fc2.bias", (NA,))]
+
+
+def _rnn_obs(name, shape, obs):
+    if not obs.is_cuda:
+        raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    if obs.dtype != torch.float32 or obs.dim() != 4 or obs.shape[2] != shape.A or obs.shape[3] != shape.OBS or \
+            obs.stride(3) != 1 or obs.stride(2) != shape.OBS:
+        raise TypeError(f"{name}: obs must be float32 [B, T, {shape.A}, {shape.OBS}] with dense [A, obs] rows")
+    return obs
+
+
+def _rnn_h0(name, shape, h0, B):
+    if h0 is None:
+        return None
+    if not h0.is_cuda:
+        raise RuntimeError("t2omca_amd ops need HIP-device tensors (no CPU fallback)")
+    if h0.dtype != torch.float32 or tuple(h0.shape) != (B, shape.A, shape.H) or h0.stride(2) != 1 or \
+            h0.stride(1) != shape.H or (B > 1 and h0.stride(0) % 4) or h0.data_ptr() % 16:
+        raise TypeError(f"{name}: expected float32 [{B}, {shape.A}, {shape.H}] with dense [A, H] rows, 16-byte "
+                        "aligned (any episode stride that is a multiple of 4)")
+    return h0
+
+
+def _rnn_actions(name, shape, actions, B, steps, need):
+    if actions is None:
+        if need:
+            raise ValueError(f"{name}: the actions are needed")
+        return None
+    _i64c(f"{name}: actions", actions)
+    if actions.shape[0] != B or actions.shape[2] != shape.A or actions.shape[1] < steps:
+        raise ValueError(f"{name}: actions must cover [{B}, >= {steps}, {shape.A}], got {tuple(actions.shape)}")
+    return actions
+
+
+def rnn_agent_fwd(shape: RnnShape, params_on, obs, *, actions=None, act_shift=0, h0_on=None, params_tg=None,
+                  h0_tg=None, steps=None, outs=None, want_x=True, timer=None):
+    """GRU agent forward (t2o_rnn_fwd) of one or two networks sharing the inputs.
+    params_*: flat parameters (dense float32, shape.n_params); obs [B, T1, A, OBS] (any
+    episode / step strides, dense [A, OBS] rows); actions int64 [B, >= T1 - 1 + act_shift,
+    A] (any episode / step strides) or None: the last-action one-hot of step t is that of
+    actions[:, t - 1 + act_shift], zero where that index is negative or actions is None.
+    h0_*: [B, A, H] (the state before the first step run) or None for zeros.
+    steps=(t0, t1): only those steps, into the given outs.  Returns a dict: q_on
+    [B, T1, A, NA], h_on [B, T1, A, H], gi_on [B, T1, A, 3H], x_on [B, T1, A, H] (want_x;
+    both kept for the backward) and q_tg, h_tg, gi_tg with two networks; outs: such a dict
+    of preallocated dense tensors."""
+    _rnn_obs("rnn_agent_fwd", shape, obs)
+    B, T1, A, _ = obs.shape
+    H, NA = shape.H, shape.NA
+    _f32c("rnn_agent_fwd: params_on", params_on, (shape.n_params,))
+    two = params_tg is not None
+    if two:
+        _f32c("rnn_agent_fwd: params_tg", params_tg, (shape.n_params,))
+    t0, t1 = (0, T1) if steps is None else (int(steps[0]), int(steps[1]))
+    if not 0 <= t0 < t1 <= T1:
+        raise ValueError(f"rnn_agent_fwd: steps {(t0, t1)} outside [0, {T1}]")
+    if shape.last_action:
+        _rnn_actions("rnn_agent_fwd", shape, actions, B, max(t1 - 1 + int(act_shift), 0), False)
+    else:
+        actions = None
+    _rnn_h0("rnn_agent_fwd: h0_on", shape, h0_on, B)
+    _rnn_h0("rnn_agent_fwd: h0_tg", shape, h0_tg, B)
+    if h0_on is not None and h0_tg is not None and B > 1 and h0_on.stride(0) != h0_tg.stride(0):
+        raise TypeError("rnn_agent_fwd: h0_on and h0_tg must share their episode stride")
+    dev = obs.device
+    if outs is None:
+        outs = {}
+    want = [("q_on", NA), ("h_on", H), ("gi_on", 3 * H)] + ([("x_on", H)] if want_x else []) + \
+        ([("q_tg", NA), ("h_tg", H), ("gi_tg", 3 * H)] if two else [])
+    for k, w in want:
+        if k not in outs:
+            outs[k] = torch.empty(B, T1, A, w, device=dev)
+        _f32c(f"rnn_agent_fwd: {k}", outs[k], (B, T1, A, w))
+    h0 = h0_on if h0_on is not None else h0_tg
+    act_sb, act_st = _mstrides(actions)
+    a = _lib.RnnFwdArgs(params_on=_p(params_on), params_tg=_p(params_tg), obs=_p(obs), obs_sb=obs.stride(0),
+                        obs_st=obs.stride(1), actions=_p(actions), act_sb=act_sb, act_st=act_st, h0_on=_p(h0_on),
+                        h0_tg=_p(h0_tg), h0_sb=h0.stride(0) if h0 is not None and B > 1 else 0,
+                        x_on=_p(outs.get("x_on") if want_x else None), gi_on=_p(outs["gi_on"]),
+                        gi_tg=_p(outs.get("gi_tg") if two else None), q_on=_p(outs["q_on"]), h_on=_p(outs["h_on"]),
+                        q_tg=_p(outs.get("q_tg") if two else None), h_tg=_p(outs.get("h_tg") if two else None),
+                        B=B, T1=T1, A=A, OBS=shape.OBS, NA=NA, H=H, last_action=int(shape.last_action),
+                        agent_id=int(shape.agent_id), act_shift=int(act_shift), t0=t0, t1=t1)
+    _mark(timer, "begin:rnn_fwd")
+    check(lib().t2o_rnn_fwd(ctypes.byref(a), stream_ptr(dev)), "rnn_agent_fwd")
+    _mark(timer, "end:rnn_fwd")
+    return outs
+
+
+def rnn_slab_count(B, T, A):
+    n = int(lib().t2o_rnn_bwd_slabs(int(B), int(T), int(A)))
+    if n < 1:
+        raise ValueError(f"rnn_slab_count: bad shape B={B} T={T} A={A}")
+    return n
+
+
+def rnn_work_floats(shape: RnnShape, B, T):
+    n = int(lib().t2o_rnn_bwd_work_floats(int(B), int(T), shape.A, shape.H))
+    if n < 1:
+        raise ValueError(f"rnn_work_floats: bad shape B={B} T={T} {shape}")
+    return n
+
+
+def rnn_agent_bwd(shape: RnnShape, params, obs, fwd, *, T=None, actions=None, act_shift=0, gchosen=None, gq=None,
+                  gh=None, h0=None, want_gh0=False, gh0=None, slabs=None, work=None, timer=None):
+    """GRU agent backward (t2o_rnn_bwd) of one network over the steps t < T (default:
+    all) of the forward `fwd` (rnn_agent_fwd's dict: x_on, gi_on, h_on) on the same obs,
+    actions, act_shift and h0.  dL/dq is either gchosen [B, T, A], the gradient at
+    actions[:, t] (the learner's form), or gq [B, T, A, NA]; gh [B, T, A, H] (optional)
+    adds dL/dh.  Returns (slabs, nslab, gh0): the partial weight-gradient slabs
+    [rnn_slab_count(B, T, A), n_params] (sum them with reduce_slabs) and dL/dh0 [B, A, H]
+    (want_gh0, else None)."""
+    _rnn_obs("rnn_agent_bwd", shape, obs)
+    B, Ts, A, _ = obs.shape
+    H, NA = shape.H, shape.NA
+    T = Ts if T is None else int(T)
+    if not 1 <= T <= Ts:
+        raise ValueError(f"rnn_agent_bwd: T={T} outside [1, {Ts}]")
+    _f32c("rnn_agent_bwd: params", params, (shape.n_params,))
+    for k, w in (("x_on", H), ("gi_on", 3 * H), ("h_on", H)):
+        _f32c(f"rnn_agent_bwd: fwd[{k!r}]", fwd[k], (B, Ts, A, w))
+    if (gchosen is None) == (gq is None):
+        raise ValueError("rnn_agent_bwd: give exactly one of gchosen and gq")
+    if gchosen is not None:
+        _f32c("rnn_agent_bwd: gchosen", gchosen, (B, T, A))
+    else:
+        _f32c("rnn_agent_bwd: gq", gq, (B, T, A, NA))
+    if gh is not None:
+        _f32c("rnn_agent_bwd: gh", gh, (B, T, A, H))
+    if shape.last_action or gchosen is not None:
+        need = T if gchosen is not None else max(T - 1 + int(act_shift), 0)
+        _rnn_actions("rnn_agent_bwd", shape, actions, B, need, gchosen is not None)
+    else:
+        actions = None
+    _rnn_h0("rnn_agent_bwd: h0", shape, h0, B)
+    dev = obs.device
+    nslab, nwork = rnn_slab_count(B, T, A), rnn_work_floats(shape, B, T)
+    if slabs is None:
+        slabs = torch.empty(nslab * shape.n_params, device=dev)
+    if work is None:
+        work = torch.empty(nwork, device=dev)
+    if want_gh0 and gh0 is None:
+        gh0 = torch.empty(B, A, H, device=dev)
+    _f32c("rnn_agent_bwd: slabs", slabs)
+    _f32c("rnn_agent_bwd: work", work)
+    if gh0 is not None:
+        _f32c("rnn_agent_bwd: gh0", gh0, (B, A, H))
+    if slabs.numel() < nslab * shape.n_params or work.numel() < nwork:
+        raise ValueError("rnn_agent_bwd: the slab or work buffer is too small")
+    act_sb, act_st = _mstrides(actions)
+    a = _lib.RnnBwdArgs(params=_p(params), obs=_p(obs), obs_sb=obs.stride(0), obs_st=obs.stride(1),
+                        actions=_p(actions), act_sb=act_sb, act_st=act_st, h0=_p(h0),
+                        h0_sb=h0.stride(0) if h0 is not None and B > 1 else 0, x=_p(fwd["x_on"]), gi=_p(fwd["gi_on"]),
+                        h=_p(fwd["h_on"]), gchosen=_p(gchosen), gq=_p(gq), gh=_p(gh), gh0=_p(gh0), gslabs=_p(slabs),
+                        work=_p(work), work_floats=work.numel(), max_slabs=slabs.numel() // shape.n_params, B=B, T=T,
+                        Ts=Ts, A=A, OBS=shape.OBS, NA=NA, H=H, last_action=int(shape.last_action),
+                        agent_id=int(shape.agent_id), act_shift=int(act_shift))
+    _mark(timer, "begin:rnn_bwd")
+    check(lib().t2o_rnn_bwd(ctypes.byref(a), stream_ptr(dev)), "rnn_agent_bwd")
+    _mark(timer, "end:rnn_bwd")
+    return slabs, nslab, gh0

@@ -33,6 +33,12 @@ applies the noisy head to each step's h before select_actions (one more launch p
 step, t2o_noisy_head_fwd); the ε schedule still applies as configured.  test_mode
 runs the mean head, which is the fused step: no new launch.
 
+A GRU agent (modules.RNNAgent, ``agent.kind`` "rnn") steps on its own
+kernels (t2o_rnn_fwd with one step, two launches, no pack): it takes the env's
+observation in either mode (entity [A, 9A] or flat [A, 6]; its input width is checked
+against the env), and the kernels add the one-hots of the previous step's actions (zeros
+at t = 0) and of the agent index as the agent's flags ask.  The replay batch is the same.
+
 compact_obs=True (the env must be a VecEnv(wire=True)): the
 batch carries the observation wire format instead of the dense obs —
 ``obs_wire`` [n, T+1, A, 4] int32 plus the per-episode normaliser snapshot
@@ -104,20 +110,29 @@ class RolloutRunner:
         # the data-parallel rank is always mixed in (rank 0 keeps `seed`), so ranks given
         # the same explicit seed still draw different streams
         seed = rank_seed(0 if seed is None else seed, dist_rank())
-        if not getattr(env, "obs_entity_mode", True):
+        self.rnn = getattr(agent, "kind", "transformer") == "rnn"
+        entity = bool(getattr(env, "obs_entity_mode", True))
+        if not entity and not self.rnn:
             raise ValueError("the transformer agent reads entity observations (VecEnv obs_entity_mode=True)")
         if compact_obs and getattr(env, "wire", None) is None:
             raise ValueError("compact_obs needs a VecEnv built with wire=True")
         self.compact_obs = bool(compact_obs)
-        if env.A != agent.shape.n_ent or env.n_actions != agent.shape.NA:
+        self.n_obs = 9 * env.A if entity else 6
+        if env.A != (agent.shape.A if self.rnn else agent.shape.n_ent) or env.n_actions != agent.shape.NA:
             raise ValueError("agent and env disagree on agents / actions")
+        if self.rnn and agent.shape.OBS != self.n_obs:
+            sh = agent.shape
+            raise ValueError(f"the rnn agent's input is {sh.IN} wide ({sh.OBS} of it the observation), the env's "
+                             f"observation is {self.n_obs} wide: with its flags the agent's input_shape must be "
+                             f"{self.n_obs + sh.IN - sh.OBS}")
         self.agent, self.env = agent, env
         # a NoisyNet head (modules.TransformerAgent, action_selector "noisy-new"): non-test
         # runs explore through it (noise kind "runner", seed = this runner's, counter =
         # episode), under the ε schedule as configured; test runs use the mean head
         self.noisy = bool(getattr(agent, "noisy", False))
         self.precision = precision
-        self.shape = dataclasses.replace(agent.shape, prec=1) if precision == "bf16" else agent.shape
+        # (the GRU agent's kernels are fp32 in both precisions)
+        self.shape = dataclasses.replace(agent.shape, prec=1) if precision == "bf16" and not self.rnn else agent.shape
         self.n, self.T, self.A, self.NA = env.n_envs, env.T, env.A, env.n_actions
         self.device = env.device
         self.schedule = LinearSchedule(epsilon_start, epsilon_finish, epsilon_anneal_time)
@@ -150,7 +165,7 @@ class RolloutRunner:
             obs = dict(obs_wire=torch.empty(T1, n, A, 4, dtype=torch.int32, device=dev))
             self._obs_step = torch.empty(n, A, 9 * A, device=dev)
         else:
-            obs = dict(obs=torch.empty(T1, n, A, 9 * A, device=dev))
+            obs = dict(obs=torch.empty(T1, n, A, self.n_obs, device=dev))
         return dict(
             **obs,
             state=torch.empty(T1, n, 8 * A, device=dev),
@@ -171,7 +186,11 @@ class RolloutRunner:
         tm = self._bufs
         env, shape = self.env, self.shape
         flat = torch.cat([p.detach().reshape(-1) for p in self.agent.parameters()])
-        pack = ops.pack_params(shape, flat[:shape.n_params])  # (a noisy agent's sigmas follow the plain prefix)
+        if self.rnn:  # (no pack; two sets of step outputs, so that a step never writes the h it reads)
+            step_outs = [{k: torch.empty(self.n, 1, self.A, w, device=self.device)
+                          for k, w in (("q_on", shape.NA), ("h_on", shape.H), ("gi_on", 3 * shape.H))} for _ in (0, 1)]
+        else:
+            pack = ops.pack_params(shape, flat[:shape.n_params])  # (a noisy agent's sigmas follow the plain prefix)
         eps = 0.0 if test_mode else self.schedule.eval(self.t_env)
         noise = head = None
         if self.noisy and not test_mode:
@@ -187,8 +206,14 @@ class RolloutRunner:
             timer = self.timer if self.timer is not None and t % self.timer_every == 0 else None
             mark = timer or (lambda tag: None)
             obs_t = self._obs_step if self.compact_obs else tm["obs"][t]
-            q, h_seq = ops.agent_unroll_fwd(shape, pack, obs_t.unsqueeze(1), h0_on=h, timer=timer)
-            h = h_seq.view(self.n * self.A, shape.E)
+            if self.rnn:
+                prev = tm["actions"][t - 1, :, :, 0].unsqueeze(1) if t > 0 and shape.last_action else None
+                out = ops.rnn_agent_fwd(shape, flat, obs_t.unsqueeze(1), actions=prev, act_shift=1, h0_on=h,
+                                        outs=step_outs[t % 2], want_x=False, timer=timer)
+                q, h = out["q_on"], out["h_on"][:, 0]
+            else:
+                q, h_seq = ops.agent_unroll_fwd(shape, pack, obs_t.unsqueeze(1), h0_on=h, timer=timer)
+                h = h_seq.view(self.n * self.A, shape.E)
             if noise is not None:  # the noisy head's q over the fused step's mean-head q
                 ops.noisy_head_fwd(h_seq, q, *head, eps=(noise[0][t:t + 1], noise[1][t:t + 1]), timer=timer)
             counter = (self.episode * (self.T + 1) + t)
