@@ -138,13 +138,20 @@ T2O_DEV void post_fwd_pf(const Wts<__bf16>& P, const t2o_layout& L, int d, const
   f4 r1[ET], y[ET], xh1[ET], f1[FT], r2[ET], xh2[ET], ga[ET], be[ET];
   float rs1, rs2;
   bf4 zb[HET], yb[ET], fb[FT];
+  // swizzles per product (T2O_SWZ_HOIST 0): one opaque lane id for the block half's
+  // fetches, which then share the row and swizzle arithmetic (wfrag_lane)
+  constexpr bool HOIST = T2O_SWZ_HOIST;
+  [[maybe_unused]] int l = 0;
+  if constexpr (!HOIST) l = wfrag_lane();
 #pragma unroll
   for (int t = 0; t < ET; ++t) r1[t] = bu[t] + x[t];
 #pragma unroll
   for (int i = 0; i < HET; ++i) zb[i] = to_bf4(z[i]);
-  matvec_b<ET, HET, T2O_SWZ_HOIST, true>(P.w + L.N[d], HET * 16, nh, zb, r1, P.vol);
+  if constexpr (HOIST) matvec_b<ET, HET, HOIST, true>(P.w + L.N[d], HET * 16, nh, zb, r1, P.vol);
+  else matvec_b<ET, HET, true>(P.w + L.N[d], HET * 16, nh, zb, r1, P.vol, l);
   WFrag<ET> w1h;
-  wfrag_load<ET>(P.w + L.W1[d], ET * 16, 0, w1h, P.vol);
+  if constexpr (HOIST) wfrag_load<ET>(P.w + L.W1[d], ET * 16, 0, w1h, P.vol);
+  else wfrag_load<ET>(P.w + L.W1[d], ET * 16, 0, w1h, P.vol, l);
 #pragma unroll
   for (int t = 0; t < ET; ++t) {
     ga[t] = vec_t(P.v + L.g1[d], t);
@@ -156,9 +163,11 @@ T2O_DEV void post_fwd_pf(const Wts<__bf16>& P, const t2o_layout& L, int d, const
   layernorm_fwd<ET>(r1, ga, be, y, xh1, rs1);
 #pragma unroll
   for (int i = 0; i < ET; ++i) yb[i] = to_bf4(y[i]);
-  matvec_b<FT, ET, T2O_SWZ_HOIST, true>(P.w + L.W1[d], ET * 16, w1h, yb, f1, P.vol);
+  if constexpr (HOIST) matvec_b<FT, ET, HOIST, true>(P.w + L.W1[d], ET * 16, w1h, yb, f1, P.vol);
+  else matvec_b<FT, ET, true>(P.w + L.W1[d], ET * 16, w1h, yb, f1, P.vol, l);
   WFrag<FT> w2h;
-  wfrag_load<FT>(P.w + L.W2[d], FT * 16, 0, w2h, P.vol);
+  if constexpr (HOIST) wfrag_load<FT>(P.w + L.W2[d], FT * 16, 0, w2h, P.vol);
+  else wfrag_load<FT>(P.w + L.W2[d], FT * 16, 0, w2h, P.vol, l);
 #pragma unroll
   for (int t = 0; t < ET; ++t) r2[t] = vec_t(P.v + L.c2[d], t);
   wfrag_pin();
@@ -170,7 +179,8 @@ T2O_DEV void post_fwd_pf(const Wts<__bf16>& P, const t2o_layout& L, int d, const
     fb[t] = lo4(v);
     fb[t + 1] = hi4(v);
   }
-  matvec_b<ET, FT, T2O_SWZ_HOIST, true>(P.w + L.W2[d], FT * 16, w2h, fb, r2, P.vol);
+  if constexpr (HOIST) matvec_b<ET, FT, HOIST, true>(P.w + L.W2[d], FT * 16, w2h, fb, r2, P.vol);
+  else matvec_b<ET, FT, true>(P.w + L.W2[d], FT * 16, w2h, fb, r2, P.vol, l);
   next();
 #pragma unroll
   for (int t = 0; t < ET; ++t) {

@@ -385,6 +385,36 @@ T2O_DEV void matvec_b(const __bf16* __restrict__ W, int ldw, const WFrag<IT>& he
 #pragma unroll
   for (int o = 0; o < OT; ++o) y[o] = wfrag_tile<IT>(o ? rest[o - 1] : head, xb, ACC ? y[o] : zero4());
 }
+// The same with the lane id given (per-product swizzles, T2O_SWZ_HOIST 0: the mixer
+// forward).  There every wfrag_load above derives row and swizzle afresh from an opaque
+// lane id — per tile, where matvec_b does it per product; one wfrag_lane() serves
+// all the fetches of a product or of a block half, which then share that arithmetic.
+T2O_DEV int wfrag_lane() {
+  int l = threadIdx.x;
+  asm volatile("" : "+v"(l));  // (see matvec_b)
+  return l;
+}
+template <int IT>
+T2O_DEV void wfrag_load(const __bf16* __restrict__ W, int ldw, int o, WFrag<IT>& F, bool vol, int l) {
+  const int c = l & 15, g = (l >> 4) & 3;
+  const int xs = bf_swz(c, ldw);
+  const __bf16* row = W + (size_t)(16 * o + c) * ldw;
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const __bf16* p = row + ((16 * i + 4 * g) ^ xs);
+    F.f[i] = vol ? ldw4(p) : ldb4(p);
+  }
+}
+template <int OT, int IT, bool ACC = false>
+T2O_DEV void matvec_b(const __bf16* __restrict__ W, int ldw, const WFrag<IT>& head, const bf4* xb, f4* y, bool vol,
+                      int l) {
+  WFrag<IT> rest[OT > 1 ? OT - 1 : 1];
+#pragma unroll
+  for (int o = 1; o < OT; ++o) wfrag_load<IT>(W, ldw, o, rest[o - 1], vol, l);
+  if constexpr (OT > 1) wfrag_pin();
+#pragma unroll
+  for (int o = 0; o < OT; ++o) y[o] = wfrag_tile<IT>(o ? rest[o - 1] : head, xb, ACC ? y[o] : zero4());
+}
 
 // The kernels' weight view: matrices (fp32 or bf16) and vectors (always fp32).
 template <typename WT>

@@ -20,6 +20,16 @@
 using namespace t2o;
 
 namespace {
+// Weight fragments fetched one product ahead of their MFMA (mixer_block_fwd_pf,
+// t2o_mixer_block.hpp): the bf16 single-query-tile instances of 8 agents
+// (exact and runtime capacity) with the weights in LDS.  They compile well under the
+// 512-thread bound's 256 registers and the grid gives two waves per SIMD whatever the
+// count, so the fragments held ahead cost no occupancy (tools/regs.sh,
+// profiles/mixer_wfrag/).  fp32, weights read through L2, the multi-tile mixers and
+// the other agent counts keep the reads at their use.
+template <int E, int A, bool WLDS, typename WT>
+constexpr bool MIXER_FWD_WPF = sizeof(WT) == 2 && WLDS && A == 8 && MixDims<E, A>::QT == 1;
+
 // RT (t2o_dispatch.hpp RTM_): 0 exact agent count A + abs head; 1 runtime-agent
 // instance (A a capacity, args.na the agent count) + runtime head; 2 exact A +
 // runtime head (L.pos_func)
@@ -62,13 +72,31 @@ __global__ __launch_bounds__(LB) void mixer_fwd_kernel(MixerFwdArgs args) {
   }
   MixIn<E, A> in;
   mix_load<E, A>(args, n, b, 0, in, na);
+  // WPF: the head tile of each block's M is fetched under the LN2 before it; a step's
+  // first fetch — the state embedding's fragments and bias, block 0's M — under the
+  // last LN2 of the step before (the weights do not change over t; the fetch after a
+  // network's last step reads the same LDS image)
+  constexpr bool WPF = MIXER_FWD_WPF<E, A, WLDS, WT>;
+  [[maybe_unused]] WFrag<ET> mh;
+  [[maybe_unused]] WFrag<1> weh[ET];
+  [[maybe_unused]] f4 beh[ET];
+  [[maybe_unused]] auto fetch_step = [&](const auto& Q) {
+    const int l = wfrag_lane();
+#pragma unroll
+    for (int ft = 0; ft < ET; ++ft) wfrag_load<1>(Q.w + L.We, 16, ft, weh[ft], Q.vol, l);
+#pragma unroll
+    for (int ft = 0; ft < ET; ++ft) beh[ft] = vec_t(Q.v + L.be, ft);
+    wfrag_load<ET>(Q.w + L.M[0], E, 0, mh, Q.vol, l);
+  };
+  if constexpr (WPF) fetch_step(P0);
   for (int t = 0; t < n.T; ++t) {
     T2O_MARK(0);
     const Wts<WT> P = step_view(P0);
     // (swizzles per product, as the BPTT kernels: hoisted — 190 VGPRs, 5 % fewer
     // instructions per step — the kernel measured slower, 0.488 -> 0.512 ms,
     // interleaved A/B, profiles/r4_c/)
-    mix_keys<E, A>(P, L, in, X0, na);
+    if constexpr (WPF) mix_keys_pf<E, A>(weh, beh, in, X0, na);
+    else mix_keys<E, A>(P, L, in, X0, na);
     const float myq = mix_qv<E, A>(n, in, args.n_actions, args.avail != nullptr);
     __builtin_amdgcn_sched_barrier(0);  // every read of this step's inputs issued before they are reloaded
     if (t + 1 < n.T) mix_load<E, A>(args, n, b, t + 1, in, na);  // prefetch step t+1 (in is consumed)
@@ -92,7 +120,14 @@ __global__ __launch_bounds__(LB) void mixer_fwd_kernel(MixerFwdArgs args) {
 #pragma unroll
           for (int ft = 0; ft < ET; ++ft) st4(xm + 16 * ft + 4 * g, x[ft]);
         }
-        mixer_block_fwd<E, H, Dm::KT, FF, false>(P, L, d, K, lk, x, nullptr);
+        if constexpr (WPF) {
+          mixer_block_fwd_pf<E, H, Dm::KT, FF>(P, L, d, K, lk, x, mh, [&] {
+            if (d + 1 < D) wfrag_load<ET>(P.w + L.M[d + 1], E, 0, mh, P.vol);
+            else fetch_step(P);  // the next step's
+          });
+        } else {
+          mixer_block_fwd<E, H, Dm::KT, FF, false>(P, L, d, K, lk, x, nullptr);
+        }
         if (qt == 0) T2O_MARK(2 + d);
       }
 #pragma unroll

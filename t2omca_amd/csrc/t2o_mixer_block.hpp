@@ -389,6 +389,41 @@ T2O_DEV void mixer_block_fwd_lean(const Wts<WT>& P, const t2o_layout& L, int d,
   post_fwd_lean<E, H, FF>(P, L, d, z, x, &cache.post, rec);
 }
 
+// mixer_block_fwd (bf16, no cache) with every product's head fragments fetched one
+// product ahead of their MFMA (wfrag_load, t2o_common.hpp).  mh: in, the
+// head tile of this block's M, fetched by the caller (under the previous block's
+// LN2, or at the end of the step before).  N's head tile and its bias are fetched
+// after M's MFMAs, so the H heads' key products and softmaxes cover them;
+// post_fwd_pf fetches W1 / W2 and the vectors, and next() — the caller's fetch
+// for the product after the block — under LN2.  The same reads, MFMAs, operands
+// and chains as mixer_block_fwd.
+template <int E, int H, int KT, int FF, typename Next>
+T2O_DEV void mixer_block_fwd_pf(const Wts<__bf16>& P, const t2o_layout& L, int d, const KeyFrags<E, KT, true>& K,
+                                int Lk, f4* x, const WFrag<E / 16>& mh, Next&& next) {
+  constexpr int ET = E / 16, HET = H * ET;
+  f4 u[HET];
+  bf4 xb[ET];
+#pragma unroll
+  for (int i = 0; i < ET; ++i) xb[i] = to_bf4(x[i]);
+  const int l = wfrag_lane();  // one lane id for M's remaining tiles and N's head tile
+  matvec_b<HET, ET>(P.w + L.M[d], E, mh, xb, u, P.vol, l);
+  WFrag<HET> nh;
+  f4 bu[ET];
+  wfrag_load<HET>(P.w + L.N[d], HET * 16, 0, nh, P.vol, l);
+#pragma unroll
+  for (int t = 0; t < ET; ++t) bu[t] = vec_t(P.v + L.bu[d], t);
+  wfrag_pin();
+  f4 z[HET];
+#pragma unroll
+  for (int hh = 0; hh < H; ++hh) {
+    f4 s[KT];
+    attn_probs(K, &u[hh * ET], Lk, s);
+    keys_combine(K, s, &z[hh * ET]);
+  }
+  wfrag_pin();  // (else bu + x is scheduled up to the fetch and waits for it there)
+  post_fwd_pf<E, H, FF>(P, L, d, z, x, nh, bu, next);
+}
+
 template <int E, int H, int KT, int FF, typename WT, int CP, int KM = 0>
 T2O_DEV void mixer_block_bwd_lean(const Wts<WT>& P, const t2o_layout& L, float* __restrict__ gs,
                                   const MaskedRec<WT, CP>& rec, float* __restrict__ stage, int d,

@@ -231,6 +231,30 @@ T2O_DEV void mix_keys(const Wts<WT>& P, const t2o_layout& L, const In& in, float
   }
 }
 
+// mix_keys (bf16, one state tile) from the embedding's fragments and bias fetched by
+// the caller a step ahead (wfrag_load(We, 16, ft, we[ft]), vec_t(be, ft); the forward
+// kernel's prefetching instances, t2o_mixer.hip): the same MFMAs on the same operands.
+template <int E, int A, typename In>
+T2O_DEV void mix_keys_pf(const WFrag<1> (&we)[E / 16], const f4 (&be)[E / 16], const In& in, float* X0, int na) {
+  using Dm = MixDims<E, A>;
+  static_assert(Dm::ST == 1, "one state tile");
+  constexpr int ET = E / 16;
+  const int c = lane_c(), g = lane_g(), lane = threadIdx.x & 63;
+  const bf4 sb = to_bf4(in.st[0]);
+  f4 emb[ET];
+#pragma unroll
+  for (int ft = 0; ft < ET; ++ft) emb[ft] = wfrag_tile<1>(we[ft], &sb, zero4());
+  if (c < na) {
+#pragma unroll
+    for (int ft = 0; ft < ET; ++ft) st4(X0 + c * Dm::LDX + 16 * ft + 4 * g, emb[ft] + be[ft]);
+  }
+#pragma unroll
+  for (int k = 0; k < MixIn<E, A>::HV; ++k) {
+    const int i = lane + 64 * k;
+    if (i < na * E / 4) st4(X0 + (na + (4 * i) / E) * Dm::LDX + (4 * i) % E, in.hid[k]);
+  }
+}
+
 // Mixing head (n_transf_mixer.py:75-89, pos_func abs: t2o_layout_init lays out
 // every other qmix_pos_func generic) on the final query rows OUT[q][f],
 // lanes = features.  Returns y; writes hyper tokens back into X0.
