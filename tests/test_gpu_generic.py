@@ -132,7 +132,7 @@ def mixer_module_check(path):
 RELU_MARGIN = 1e-6
 
 
-def _td(cfg, B, T, precision="fp32", seed=3, tol=None):
+def _td(cfg, B, T, precision="fp32", seed=3, tol=None, prepare=None, pipeline=None):
     """GPU TD update vs the fp64 oracle for a model described by cfg (bars: tol =
     (forward, gradient), default the fp32 (1e-5, 3e-5)); returns the learner and the
     errors.  fp32: the oracle's ReLU is tie-aware (tests/gpu_util.oracle_td_tie_aware):
@@ -144,7 +144,10 @@ def _td(cfg, B, T, precision="fp32", seed=3, tol=None):
     tie-aware reference; bf16 relative L2 <= max(2^-8, 4 x the error of the oracle run
     with bf16 matmul operands on this same case).  For that the inputs must leave no
     block's reference gradient (near) zero, which was computed without a device: the
-    batch is drawn on the CPU, and the modules with grad_blocks.module_seed(A)."""
+    batch is drawn on the CPU, and the modules with grad_blocks.module_seed(A).
+    prepare: a callable applied to (agent, mixer) after construction, before their
+    parameters are read and the learner is built (tests/sharp.sharpen_); pipeline: the
+    learner's `pipeline` argument, if not its default."""
     from t2omca_amd.learner import TDLearner
     from t2omca_amd.modules import TransformerAgent, TransformerMixer
     from t2omca_amd.synthetic import make_batch
@@ -152,9 +155,11 @@ def _td(cfg, B, T, precision="fp32", seed=3, tol=None):
     torch.manual_seed(module_seed(A))
     args = _args(cfg)
     agent, mixer = TransformerAgent(None, args).cuda(), TransformerMixer(args).cuda()
+    if prepare is not None:
+        prepare(agent, mixer)
     pa = {k: v.detach().cpu().double() for k, v in agent.state_dict().items()}
     pm = {k: v.detach().cpu().double() for k, v in mixer.state_dict().items()}
-    learner = TDLearner(agent, mixer, precision=precision)
+    learner = TDLearner(agent, mixer, precision=precision, **({} if pipeline is None else dict(pipeline=pipeline)))
     cpu, w = make_batch(B, T, A, seed=seed, obs_feats=9, state_feats=8, device="cpu")
     batch, w = {k: v.cuda() for k, v in cpu.items()}, w.cuda()
     info = learner.train(batch, 0, 0, per_weight=w)
