@@ -281,7 +281,14 @@ int t2o_agent_bwd_ranges(const t2o_layout* L, int has_hmid);
  * chosen-Q gather / double-Q argmax.  qmode: 0 = qvals given (qv_* [B][T][A]);
  * 1 = chosen-action gather from the network's Q array (q_on / q_tg
  * [b][q_ts][a][n_actions] at actions); 2 = double-Q: the network's Q array at
- * argmax_a' of q_on masked by avail (NULL = all available), ties -> lowest index. */
+ * argmax_a' of q_on masked by avail (NULL = all available), ties -> lowest index.
+ * Limits: with qmode 1 or 2 on either network, 1 <= n_actions <= t2o_mixer_max_actions()
+ * (8: each lane of the MFMA instances keeps the Q row of its agent in registers),
+ * T2O_EUNSUPPORTED otherwise; the runtime-shaped kernels (generic = 1) read the rows from
+ * memory and take n_actions <= 64.  qmode 0 reads no Q array and has no such limit (the
+ * agent head's NA <= 16 is the only one).  The flat mixers' selection (t2o_q_select,
+ * t2o_qplex_select) takes NA <= 16. */
+int t2o_mixer_max_actions(void);
 typedef struct {
   const t2o_layout* L;
   const float* pack_on;

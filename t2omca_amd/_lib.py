@@ -147,6 +147,7 @@ EXPORTS = {
     "t2o_mixer_unroll_bwd": (ctypes.c_int, [ctypes.POINTER(MixerBwdArgs), ctypes.c_void_p]),
     "t2o_mixer_bwd_work_floats": (ctypes.c_int64, [ctypes.POINTER(Layout), ctypes.c_int, ctypes.c_int]),
     "t2o_mixer_split": (ctypes.c_int, [ctypes.POINTER(Layout), ctypes.c_int]),
+    "t2o_mixer_max_actions": (ctypes.c_int, []),
     "t2o_mixer_bwd_max_slabs": (ctypes.c_int, [ctypes.c_int]),
     "t2o_bwd_tape_floats": (ctypes.c_int64, [ctypes.POINTER(Layout), ctypes.c_int64]),
     "t2o_bwd_tape_tiles": (ctypes.c_int64, [ctypes.POINTER(Layout), ctypes.c_int, ctypes.c_int, ctypes.c_int]),

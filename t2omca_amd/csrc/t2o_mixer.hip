@@ -958,6 +958,9 @@ extern "C" int t2o_mixer_unroll_fwd(const t2o_mixer_fwd_args* a, void* stream) {
                         a->xout_tg, a->xmid_tg, a->B, a->T_on, a->T_tg, ph, ph ? a->t0 : 0, ph ? a->t1 : 0, stream);
 }
 
+// the widest Q row the unroll's chosen-Q gather / double-Q argmax takes (qmode 1, 2)
+extern "C" int t2o_mixer_max_actions(void) { return MIX_MAXNA; }
+
 // worst case: 1 episode per workgroup, plus the decoupled multi-tile mixer's
 // parallel workgroups (t2o_mixer_split.hip) at the batches it runs at
 extern "C" int t2o_mixer_bwd_max_slabs(int B) { return B + t2o::mixer_split_extra_slabs(B); }

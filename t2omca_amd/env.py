@@ -71,7 +71,9 @@ class VecEnv:
             raise RuntimeError("VecEnv runs on the HIP device only (the numpy restatement in oracle/ is test-only)")
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        # n_actions = num_channels + 1 must fit the agent head (t2o_layout_init: NA <= 16)
+        # n_actions = num_channels + 1 must fit the agent head (t2o_layout_init: NA <= 16).  The
+        # transformer mixer's MFMA kernels select among fewer (t2o_mixer_max_actions() = 8, so
+        # num_channels <= 7 under them: TDLearner refuses the rest); qmix, vdn and dmaq take 16
         if not (1 <= agv_num <= 64 and 1 <= mec_num <= 16 and 1 <= num_channels <= 15):
             raise ValueError("VecEnv supports agv_num <= 64, mec_num <= 16, num_channels <= 15 "
                              "(n_actions = num_channels + 1 <= 16, the agent head's limit)")

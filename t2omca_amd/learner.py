@@ -199,6 +199,16 @@ class TDLearner:
             if getattr(getattr(agent, "args", None), "action_selector", None) == "noisy-new":
                 raise ValueError("an rnn agent has no noisy head (action_selector='noisy-new' needs the "
                                  "transformer agent)")
+        # the transformer mixer's MFMA unroll selects the chosen / double-Q values from Q rows it
+        # keeps in registers, narrower than the agent head (include/t2omca.h t2o_mixer_unroll_fwd;
+        # its runtime-shaped kernels read the rows from memory and take every agent head)
+        n_actions = getattr(getattr(agent, "shape", None), "NA", None)
+        if self.mixer_kind == "transformer" and n_actions is not None and not mixer.shape.generic:
+            max_actions = int(ops.lib().t2o_mixer_max_actions())
+            if n_actions > max_actions:
+                raise ValueError(f"the transformer mixer's Q selection takes at most {max_actions} actions "
+                                 f"(t2o_mixer_max_actions), this agent has {n_actions}; the qmix, vdn and dmaq "
+                                 f"mixers take up to 16")
         dev = next(agent.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("TDLearner needs the modules on a HIP device (no CPU fallback)")

@@ -36,12 +36,16 @@ from t2omca_amd import env_spec as S  # noqa: E402
 REF = "/root/reference"
 SEED = 1234
 CONFIGS = {
-    # tag: (M, A, T, episodes, n_envs[, obs_entity_mode])
+    # tag: (M, A, T, episodes, n_envs[, obs_entity_mode[, num_channels]])
     "m2_a16_t10": (2, 16, 10, 2, 2),
     "m4_a8_t8": (4, 8, 8, 2, 2),
     "m2_a3_t6": (2, 3, 6, 3, 2),
     # get_obs_agent's flat branch (:172-182): obs = [last_ack, get_agent_inf] per agent
     "m2_a8_t8_flat": (2, 8, 8, 2, 2, False),
+    # num_channels other than 4: two actions (every offloader of a MEC collides), and
+    # utilisation terms 1/7 that are not dyadic (step :327-329)
+    "m2_a8_c1_t6": (2, 8, 6, 2, 2, True, 1),
+    "m4_a5_c7_t5": (4, 5, 5, 2, 2, True, 7),
 }
 
 
@@ -133,9 +137,9 @@ def build_pkg():
     return mod
 
 
-def run_env(mod, M, A, T, episodes, env_id, rng, obs_entity_mode=True):
+def run_env(mod, M, A, T, episodes, env_id, rng, obs_entity_mode=True, num_channels=4):
     STREAM[0] = Stream(env_id)
-    env = mod.MultiAgvOffloadingEnv(mec_num=M, agv_num=A, num_channels=4, episode_limit=T, seed=0,
+    env = mod.MultiAgvOffloadingEnv(mec_num=M, agv_num=A, num_channels=num_channels, episode_limit=T, seed=0,
                                     obs_entity_mode=obs_entity_mode, state_entity_mode=True)
     out = {"mec_index": np.array([ag.mec_index for ag in env.agents])}
     info0 = env.get_env_info()
@@ -184,13 +188,16 @@ def main(tags=None):
             continue
         M, A, T, episodes, n_envs = cfg[:5]
         ent = cfg[5] if len(cfg) > 5 else True
+        C = cfg[6] if len(cfg) > 6 else 4
         rng = np.random.default_rng(7)
         res = {"M": np.array(M), "A": np.array(A), "T": np.array(T), "episodes": np.array(episodes),
                "seed": np.array(SEED)}
         if not ent:
             res["obs_entity_mode"] = np.array(0)
+        if C != 4:  # readers take a missing key as 4
+            res["num_channels"] = np.array(C)
         for e in range(n_envs):
-            for k, v in run_env(mod, M, A, T, episodes, e, rng, ent).items():
+            for k, v in run_env(mod, M, A, T, episodes, e, rng, ent, C).items():
                 res[f"env{e}/{k}"] = v
         np.savez_compressed(os.path.join(HERE, f"env_{tag}.npz"), **res)
         print("wrote", tag)

@@ -56,6 +56,10 @@ EXTENDED = {
     "a8_quadratic": ("m", 8, 32, 3, 2, 3, 4, {"qmix_pos_func": "quadratic"}),
     "a8_identity": ("m", 8, 32, 3, 2, 3, 4, {"qmix_pos_func": "none"}),
     "a3_obsbranch": ("m", 3, 32, 3, 2, 2, 3, {"state_entity_mode": False, "state_entity_feats": 9}),
+    # action counts other than five: a Q head narrower than one 4-column group, and one
+    # whose last group is exactly full
+    "a5_na3": ("a", 5, 32, 3, 2, 2, 3, {"n_actions": 3}),
+    "a8_na8": ("a", 8, 32, 3, 2, 2, 3, {"n_actions": 8}),
 }
 
 
@@ -95,7 +99,7 @@ def make_args(A, E, H, D, extra=None):
 def cfg_of(args):
     cfg = dict(n_agents=args.n_agents, n_entities=args.n_entities, obs_entity_feats=9,
                emb=args.emb, heads=args.heads, depth=args.depth, ff_hidden_mult=args.ff_hidden_mult,
-               n_actions=5, state_entity_feats=args.state_entity_feats, mixer_emb=args.emb,
+               n_actions=args.n_actions, state_entity_feats=args.state_entity_feats, mixer_emb=args.emb,
                mixer_heads=args.heads, mixer_depth=args.depth)
     for k in ("n_entities_obs", "n_entities_state", "qmix_pos_func", "qmix_pos_func_beta"):
         if hasattr(args, k):
@@ -116,7 +120,7 @@ def gen_agent(TA, tag, A, E, H, D, b, T, seed, extra=None):
     ne = getattr(args, "n_entities_obs", A)
     obs = torch.randn(b, T, A, ne * 9, generator=g, dtype=torch.float64)
     h0 = 0.5 * torch.randn(b, A, E, generator=g, dtype=torch.float64)
-    cq = torch.randn(b, T, A, 5, generator=g, dtype=torch.float64)
+    cq = torch.randn(b, T, A, args.n_actions, generator=g, dtype=torch.float64)
     ch = torch.randn(b, T, A, E, generator=g, dtype=torch.float64)
     out = {"obs": obs.numpy(), "h0": h0.numpy(), "cq": cq.numpy(), "ch": ch.numpy(), **meta(extra)}
     for k, v in params.items():

@@ -15,7 +15,8 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 def replay(z, e):
     M, A, T, eps, seed = (int(z[k]) for k in ("M", "A", "T", "episodes", "seed"))
     ent = bool(z["obs_entity_mode"]) if "obs_entity_mode" in z.files else True
-    env = RefEnv(M, A, T, seed, e, obs_entity_mode=ent)
+    C = int(z["num_channels"]) if "num_channels" in z.files else 4
+    env = RefEnv(M, A, T, seed, e, num_channels=C, obs_entity_mode=ent)
     out = {"mec_index": env.mec_index.copy()}
     info = env.get_env_info()
     out["env_info"] = np.array([info.get(k, -1) for k in ("state_shape", "obs_shape", "n_actions", "n_agents",

@@ -16,7 +16,8 @@ TOL_F32 = 1e-5   # normwise fp32 tolerance (BASELINE.json north_star)
 
 def _shape(cfg):
     from t2omca_amd.ops import AGENT, NetShape
-    return NetShape(AGENT, cfg["emb"], cfg["heads"], cfg["depth"], 9, 5, 4 * cfg["emb"], cfg["n_entities"])
+    return NetShape(AGENT, cfg["emb"], cfg["heads"], cfg["depth"], 9, cfg.get("n_actions", 5), 4 * cfg["emb"],
+                    cfg["n_entities"])
 
 
 @pytest.mark.parametrize("path", tuned_fixtures("agent"))

@@ -41,8 +41,10 @@ def test_env_matches_reference_trajectories(path):
     z = np.load(path)
     M, A, T, eps, seed = (int(z[k]) for k in ("M", "A", "T", "episodes", "seed"))
     ent = bool(z["obs_entity_mode"]) if "obs_entity_mode" in z.files else True  # flat obs branch (:172-182)
+    C = int(z["num_channels"]) if "num_channels" in z.files else 4  # (fixtures from before the key: 4)
     NE = len({k.split("/")[0] for k in z.files if k.startswith("env")})
-    env = VecEnv(NE, mec_num=M, agv_num=A, episode_limit=T, seed=seed, keep_obs64=True, obs_entity_mode=ent)
+    env = VecEnv(NE, mec_num=M, agv_num=A, num_channels=C, episode_limit=T, seed=seed, keep_obs64=True,
+                 obs_entity_mode=ent)
     _eq(env.mec_index.cpu().numpy(), np.stack([z[f"env{e}/mec_index"] for e in range(NE)]), "mec_index")
     env.get_env_info(all_envs=True)
     gold = {k: np.stack([z[f"env{e}/{k}"] for e in range(NE)]) for k in
@@ -71,11 +73,13 @@ def test_env_matches_reference_trajectories(path):
     _eq(env.draws.cpu().numpy(), gold["draws"], "draws")
 
 
-def _rollout_vs_oracle(NE, M, A, T, eps, seed, edge_only=False, runner_info=True, obs_entity_mode=True):
+def _rollout_vs_oracle(NE, M, A, T, eps, seed, edge_only=False, runner_info=True, obs_entity_mode=True,
+                       num_channels=4):
     from t2omca_amd.env import VecEnv
-    env = VecEnv(NE, mec_num=M, agv_num=A, episode_limit=T, seed=seed, edge_only=edge_only, keep_obs64=True,
-                 obs_entity_mode=obs_entity_mode)
-    refs = [RefEnv(M, A, T, seed, e, edge_only=edge_only, obs_entity_mode=obs_entity_mode) for e in range(NE)]
+    env = VecEnv(NE, mec_num=M, agv_num=A, num_channels=num_channels, episode_limit=T, seed=seed,
+                 edge_only=edge_only, keep_obs64=True, obs_entity_mode=obs_entity_mode)
+    refs = [RefEnv(M, A, T, seed, e, num_channels=num_channels, edge_only=edge_only,
+                   obs_entity_mode=obs_entity_mode) for e in range(NE)]
     if runner_info:  # the runner's get_env_info touches env 0 only (parallel_runner.py:34)
         assert env.get_env_info() == refs[0].get_env_info()
     rng = np.random.default_rng(seed)

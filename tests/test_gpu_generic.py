@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.gpu_util import normwise, oracle_td_tie_aware, require_gpu
+from tests.gpu_util import argmax_preconditions, masked_avail, normwise, oracle_td_tie_aware, require_gpu
 from tests.grad_blocks import assert_blocks_bf16, assert_blocks_fp32, emulated_bf16_grad, module_seed
 from tests.test_oracle_golden import _cfg
 
@@ -44,7 +44,7 @@ def _args(cfg, device="cuda"):
     a = types.SimpleNamespace(
         n_agents=cfg["n_agents"], n_entities=cfg["n_entities"], obs_entity_feats=9, emb=cfg["emb"],
         heads=cfg["heads"], depth=cfg["depth"], ff_hidden_mult=cfg["ff_hidden_mult"], dropout=0.0,
-        action_selector="epsilon_greedy", n_actions=5, device=device,
+        action_selector="epsilon_greedy", n_actions=cfg.get("n_actions", 5), device=device,
         state_entity_feats=cfg["state_entity_feats"], mixer_emb=cfg["mixer_emb"], mixer_heads=cfg["mixer_heads"],
         mixer_depth=cfg["mixer_depth"], env_args={"state_entity_mode": bool(cfg.get("state_entity_mode", True))})
     for k in ("n_entities_obs", "n_entities_state", "qmix_pos_func", "qmix_pos_func_beta"):
@@ -132,7 +132,8 @@ def mixer_module_check(path):
 RELU_MARGIN = 1e-6
 
 
-def _td(cfg, B, T, precision="fp32", seed=3, tol=None, prepare=None, pipeline=None):
+def _td(cfg, B, T, precision="fp32", seed=3, tol=None, prepare=None, pipeline=None, avail_seed=None,
+        model_seed=None):
     """GPU TD update vs the fp64 oracle for a model described by cfg (bars: tol =
     (forward, gradient), default the fp32 (1e-5, 3e-5)); returns the learner and the
     errors.  fp32: the oracle's ReLU is tie-aware (tests/gpu_util.oracle_td_tie_aware):
@@ -147,12 +148,17 @@ def _td(cfg, B, T, precision="fp32", seed=3, tol=None, prepare=None, pipeline=No
     batch is drawn on the CPU, and the modules with grad_blocks.module_seed(A).
     prepare: a callable applied to (agent, mixer) after construction, before their
     parameters are read and the learner is built (tests/sharp.sharpen_); pipeline: the
-    learner's `pipeline` argument, if not its default."""
+    learner's `pipeline` argument, if not its default.  The batch has cfg["n_actions"] actions
+    (default 5), all available; with avail_seed they are masked by tests/gpu_util.masked_avail
+    under that seed, and the argmax preconditions of tests/test_gpu_learner_masks.py are
+    asserted on the oracle's Q (the masked argmax moved in >= 25 % of (b, t, a); smallest masked
+    top-two gap >= 1e-4 max|Q|), their values returned with the errors.  model_seed: the
+    modules' torch.manual_seed where grad_blocks.module_seed(A) leaves a block unfit."""
     from t2omca_amd.learner import TDLearner
     from t2omca_amd.modules import TransformerAgent, TransformerMixer
     from t2omca_amd.synthetic import make_batch
     A = cfg["n_agents"]
-    torch.manual_seed(module_seed(A))
+    torch.manual_seed(module_seed(A) if model_seed is None else model_seed)
     args = _args(cfg)
     agent, mixer = TransformerAgent(None, args).cuda(), TransformerMixer(args).cuda()
     if prepare is not None:
@@ -160,7 +166,10 @@ def _td(cfg, B, T, precision="fp32", seed=3, tol=None, prepare=None, pipeline=No
     pa = {k: v.detach().cpu().double() for k, v in agent.state_dict().items()}
     pm = {k: v.detach().cpu().double() for k, v in mixer.state_dict().items()}
     learner = TDLearner(agent, mixer, precision=precision, **({} if pipeline is None else dict(pipeline=pipeline)))
-    cpu, w = make_batch(B, T, A, seed=seed, obs_feats=9, state_feats=8, device="cpu")
+    n_actions = cfg.get("n_actions", 5)
+    cpu, w = make_batch(B, T, A, n_actions=n_actions, seed=seed, obs_feats=9, state_feats=8, device="cpu")
+    if avail_seed is not None:
+        cpu["avail_actions"] = masked_avail(B, T + 1, A, n_actions, seed=avail_seed)
     batch, w = {k: v.cuda() for k, v in cpu.items()}, w.cuda()
     info = learner.train(batch, 0, 0, per_weight=w)
     torch.cuda.synchronize()
@@ -170,6 +179,11 @@ def _td(cfg, B, T, precision="fp32", seed=3, tol=None, prepare=None, pipeline=No
     errs = dict(qtot=normwise(info["qtot"], ex["qtot"]), targets=normwise(info["targets"], ex["targets"]),
                 prio=normwise(info["td_errors_abs"], prio), grad=normwise(g, ref_g))
     print(cfg.get("tag"), precision, errs, "relu ties", ties)
+    if avail_seed is not None:
+        errs["moved"], errs["gap"] = argmax_preconditions(ex["mac_out"], cpu["avail_actions"])
+        print(cfg.get("tag"), f"argmax moved {errs['moved']:.3f} gap {errs['gap']:.2e}")
+        assert errs["moved"] >= 0.25, errs["moved"]
+        assert errs["gap"] >= 1e-4, errs["gap"]
     tf, tg = tol or (1e-5, 3e-5)
     assert errs["qtot"] < tf and errs["targets"] < tf and errs["prio"] < tf, errs
     assert errs["grad"] < tg, errs

@@ -109,11 +109,11 @@ def make_learner(cfg, model_seed=None, **kw):
     return TDLearner(agent, mixer, **kw), pa, pm
 
 
-def masked_batch(A, B, T, seed):
+def masked_batch(A, B, T, seed, n_actions=5):
     """make_batch drawn on the CPU with the masked avail_actions; CPU tensors."""
     from t2omca_amd.synthetic import make_batch
-    batch, w = make_batch(B, T, A, seed=seed, device="cpu")
-    batch["avail_actions"] = masked_avail(B, T + 1, A, seed=seed + 100)
+    batch, w = make_batch(B, T, A, n_actions=n_actions, seed=seed, device="cpu")
+    batch["avail_actions"] = masked_avail(B, T + 1, A, n_actions, seed=seed + 100)
     return batch, w
 
 

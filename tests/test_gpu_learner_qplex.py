@@ -120,15 +120,15 @@ def _oracle(monkeypatch, **kw):
     monkeypatch.setattr(ref_learner, "td_forward", qplex_model.td_forward_qplex(**kw))
 
 
-def _update(monkeypatch, tag, A, B, T, *, noisy=False, q_lambda=False, **kw):
+def _update(monkeypatch, tag, A, B, T, *, noisy=False, q_lambda=False, n_actions=NA, **kw):
     """One update from perturbed targets against the substituted oracle at the fp32 bars."""
-    cfg = _cfg_of(A)
+    cfg = _cfg_of(A, n_actions=n_actions)
     learner, pa, pm = make_learner(cfg, noisy=noisy, q_lambda=q_lambda, **kw)
     assert learner.mixer_kind == "qplex" and not learner._pipelined(B)
     assert learner.nm == sum(v.numel() for v in pm.values()) and list(pm) == qplex_model.keys(4)
     perturb_targets(learner)
     pat, pmt = split_flat(learner.target_params, pa, pm)
-    cpu, w = masked_batch(A, B, T, SEED)
+    cpu, w = masked_batch(A, B, T, SEED, n_actions)
     snap = Snapshot(learner)
     out, info = update(learner, to_cuda(cpu), w.cuda())
     noise = None

@@ -92,20 +92,20 @@ def _kernel_family(monkeypatch):
     monkeypatch.delenv("T2O_MIXER_SPLIT", raising=False)
 
 
-def modules(A, kind, device="cuda", seed=None):
+def modules(A, kind, device="cuda", seed=None, n_actions=NA):
     from t2omca_amd.modules import make_agent, make_mixer
     torch.manual_seed(module_seed(A) if seed is None else seed)
-    args = _args(_cfg_of(A), device=str(device))
+    args = _args(_cfg_of(A, n_actions=n_actions), device=str(device))
     args.mixer, args.agent = kind, "rnn"
-    agent = make_agent(9 * A + NA + A, args).to(device)
+    agent = make_agent(9 * A + n_actions + A, args).to(device)
     if kind == "qplex":  # (module docstring: the QPLEX mixer's seed)
         torch.manual_seed((module_seed(A) if seed is None else seed) + QPLEX_MIXER_SEED)
     return agent, make_mixer(args).to(device)
 
 
-def make_learner(A, kind, **kw):
+def make_learner(A, kind, seed=None, n_actions=NA, **kw):
     from t2omca_amd.learner import TDLearner
-    agent, mixer = modules(A, kind)
+    agent, mixer = modules(A, kind, seed=seed, n_actions=n_actions)
     assert agent.kind == "rnn" and mixer.kind == kind
     pa = {k: v.detach().cpu().double() for k, v in agent.state_dict().items()}
     pm = {k: v.detach().cpu().double() for k, v in mixer.state_dict().items()}
@@ -117,18 +117,19 @@ def _oracle(monkeypatch, kind, **kw):
     monkeypatch.setattr(ref_learner, "td_forward", rnn_model.td_forward_rnn(kind, **kw))
 
 
-def _update(monkeypatch, tag, kind, A, B, T, *, q_lambda=False, **kw):
+def _update(monkeypatch, tag, kind, A, B, T, *, q_lambda=False, n_actions=NA, seed=None, **kw):
     """One update from perturbed targets against the substituted oracle at the fp32 bars."""
-    learner, pa, pm = make_learner(A, kind, q_lambda=q_lambda, **kw)
+    learner, pa, pm = make_learner(A, kind, seed=seed, n_actions=n_actions, q_lambda=q_lambda, **kw)
     assert learner.agent_kind == "rnn" and learner.mixer_kind == kind and not learner._pipelined(B)
     assert list(pa) == list(rnn_model.KEYS) and learner.na == sum(v.numel() for v in pa.values())
     perturb_targets(learner)
     pat, pmt = split_flat(learner.target_params, pa, pm)
-    cpu, w = masked_batch(A, B, T, SEED)
+    cpu, w = masked_batch(A, B, T, SEED, n_actions)
     snap = Snapshot(learner)
     out, info = update(learner, to_cuda(cpu), w.cuda())
     _oracle(monkeypatch, kind, q_lambda=q_lambda)
-    errs, g, ex = check_update(f"rnn {tag} {kind}", learner, pa, pm, _cfg_of(A), cpu, w, out, pa_tgt=pat, pm_tgt=pmt)
+    errs, g, ex = check_update(f"rnn {tag} {kind}", learner, pa, pm, _cfg_of(A, n_actions=n_actions), cpu, w, out,
+                               pa_tgt=pat, pm_tgt=pmt)
     return learner, snap, out, info, ex, (cpu, w, g, pa, pm)
 
 

@@ -30,23 +30,25 @@ NA = C + 1
 GAP = 1e-4
 
 
-def make(A, n, T, entity, wire=False, flags=True, seed=0, **runner_kw):
+def make(A, n, T, entity, wire=False, flags=True, seed=0, channels=C, **runner_kw):
     from t2omca_amd.env import VecEnv
     from t2omca_amd.modules import make_agent
     from t2omca_amd.runner import RolloutRunner
     torch.manual_seed(seed)
-    args = types.SimpleNamespace(n_agents=A, n_actions=NA, agent="rnn", obs_last_action=flags, obs_agent_id=flags,
+    na = channels + 1
+    args = types.SimpleNamespace(n_agents=A, n_actions=na, agent="rnn", obs_last_action=flags, obs_agent_id=flags,
                                  device="cuda")
     n_obs = 9 * A if entity else 6
-    agent = make_agent(n_obs + ((NA + A) if flags else 0), args).cuda()
-    env = VecEnv(n, mec_num=M, agv_num=A, num_channels=C, episode_limit=T, seed=11, obs_entity_mode=entity, wire=wire)
+    agent = make_agent(n_obs + ((na + A) if flags else 0), args).cuda()
+    env = VecEnv(n, mec_num=M, agv_num=A, num_channels=channels, episode_limit=T, seed=11, obs_entity_mode=entity,
+                 wire=wire)
     return agent, env, RolloutRunner(agent, env, seed=13, compact_obs=wire, **runner_kw)
 
 
 def model_q(agent, batch, obs):
     p = rnn_model.param_dict(agent)
     sh = agent.shape
-    x = rnn_model.build_inputs(obs.cpu().double(), batch["actions"].cpu(), NA, sh.last_action, sh.agent_id)
+    x = rnn_model.build_inputs(obs.cpu().double(), batch["actions"].cpu(), sh.NA, sh.last_action, sh.agent_id)
     n, _, A, _ = x.shape
     return rnn_model.unroll(p, x, torch.zeros(n, A, sh.H, dtype=torch.float64))[0]
 

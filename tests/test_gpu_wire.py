@@ -29,12 +29,13 @@ def test_env_wire_matches_oracle_on_reference_trajectories(path):
     from t2omca_amd.env import VecEnv
     z = np.load(path)
     M, A, T, eps, seed = (int(z[k]) for k in ("M", "A", "T", "episodes", "seed"))
+    C = int(z["num_channels"]) if "num_channels" in z.files else 4  # (fixtures from before the key: 4)
     NE = len({k.split("/")[0] for k in z.files if k.startswith("env")})
-    env = VecEnv(NE, mec_num=M, agv_num=A, episode_limit=T, seed=seed, wire=True)
+    env = VecEnv(NE, mec_num=M, agv_num=A, num_channels=C, episode_limit=T, seed=seed, wire=True)
     env.get_env_info(all_envs=True)
     refs = []
     for e in range(NE):
-        r = RefEnv(M, A, T, seed, e)
+        r = RefEnv(M, A, T, seed, e, num_channels=C)
         r.get_env_info()
         refs.append(ref_wire.record_episodes(r, z[f"env{e}/actions"], eps))
     k = 0
@@ -57,10 +58,15 @@ def test_env_wire_matches_oracle_on_reference_trajectories(path):
 
 @pytest.mark.parametrize("NE,M,A,T,eps", [(96, 2, 8, 12, 2), (40, 4, 16, 9, 2), (12, 16, 64, 5, 2), (5, 3, 3, 7, 3)])
 def test_obs_expand_reproduces_env_obs(NE, M, A, T, eps):
+    obs_expand_vs_env(NE, M, A, T, eps)
+
+
+def obs_expand_vs_env(NE, M, A, T, eps, num_channels=4):
     require_gpu()
     from t2omca_amd import ops
     from t2omca_amd.env import VecEnv
-    env = VecEnv(NE, mec_num=M, agv_num=A, episode_limit=T, seed=7, keep_obs64=True, wire=True)
+    env = VecEnv(NE, mec_num=M, agv_num=A, num_channels=num_channels, episode_limit=T, seed=7, keep_obs64=True,
+                 wire=True)
     env.get_env_info()
     rng = np.random.default_rng(1)
     for _ in range(eps):

@@ -91,3 +91,30 @@ def test_learner_rejects_bad_options_before_any_device_work():
             TDLearner(agent, mixer, **kw)
     with pytest.raises(RuntimeError, match="HIP device"):  # valid options, CPU modules: no fallback
         TDLearner(agent, mixer, td_algo="wave")
+
+
+def test_learner_refuses_more_actions_than_the_transformer_mixer_selects(monkeypatch):
+    """The transformer mixer's MFMA unroll selects among at most t2o_mixer_max_actions()
+    actions (t2o_mixer_unroll_fwd returns T2O_EUNSUPPORTED past it): a learner whose agent
+    has more is refused at construction, naming both numbers and the mixers that take 16,
+    not inside its first train().  At the limit, and with the flat mixers past it, the
+    constructor goes on to its device check."""
+    import pytest
+    from t2omca_amd import _lib
+    from t2omca_amd.learner import TDLearner
+    from t2omca_amd.modules import TransformerAgent, TransformerMixer, make_mixer
+    from t2omca_amd.synthetic import make_args
+    monkeypatch.setenv("T2O_GENERIC", "0")
+    limit = int(_lib.lib().t2o_mixer_max_actions())
+    assert 1 <= limit < 16
+    for na in (limit + 1, 16):
+        args = make_args(8, n_actions=na, device="cpu")
+        with pytest.raises(ValueError, match=rf"(?s)at most {limit} actions.*has {na}.*qmix, vdn and dmaq.*16"):
+            TDLearner(TransformerAgent(None, args), TransformerMixer(args))
+    args = make_args(8, n_actions=limit, device="cpu")
+    with pytest.raises(RuntimeError, match="HIP device"):
+        TDLearner(TransformerAgent(None, args), TransformerMixer(args))
+    for kind in ("qmix", "vdn", "dmaq"):
+        args = make_args(8, n_actions=16, device="cpu", mixer=kind)
+        with pytest.raises(RuntimeError, match="HIP device"):
+            TDLearner(TransformerAgent(None, args), make_mixer(args))

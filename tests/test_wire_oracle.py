@@ -18,8 +18,9 @@ def test_wire_expand_reproduces_reference_obs(path):
     z = np.load(path)
     M, A, T, eps, seed = (int(z[k]) for k in ("M", "A", "T", "episodes", "seed"))
     n_envs = len({k.split("/")[0] for k in z.files if k.startswith("env")})
+    C = int(z["num_channels"]) if "num_channels" in z.files else 4
     for e in range(n_envs):
-        env = RefEnv(M, A, T, seed, e)
+        env = RefEnv(M, A, T, seed, e, num_channels=C)
         env.get_env_info()  # the runner's start-up call (parallel_runner.py:34)
         rec = ref_wire.record_episodes(env, z[f"env{e}/actions"], eps)
         gold = z[f"env{e}/obs"].reshape(eps, T + 1, A, 9 * A)
