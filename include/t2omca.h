@@ -936,6 +936,14 @@ int t2o_probe_scatter_ops(const float* in, float* out, void* stream);
  * [12][nwaves][64][4] floats (t2o_probe.hip). */
 int t2o_probe_xdl_hazards(const float* in, float* out, int nwaves, void* stream);
 
+/* Diagnostic: stale-LDS probes (t2o_probe.hip, tests/test_gpu_stale_lds.py).  Each
+ * workgroup takes the full 160 KB of dynamic LDS, so one fits per CU.
+ * t2o_probe_lds_fill stores `word` into every 32-bit word of its LDS and exits;
+ * t2o_probe_lds_census writes nothing to LDS and stores in out[workgroup] (device,
+ * int32[workgroups]) how many words of its allocation differ from `word`. */
+int t2o_probe_lds_fill(uint32_t word, int workgroups, void* stream);
+int t2o_probe_lds_census(uint32_t word, int workgroups, int32_t* out, void* stream);
+
 /* Diagnostic: the XOR (in bf16 elements, a multiple of 8) applied to the
  * columns of row `row` of a bf16 weight-image matrix with row length ld: element
  * (r, col) of the image sits at r*ld + (col ^ t2o_bf_swz(r, ld)). */

@@ -193,6 +193,8 @@ EXPORTS = {
     "t2o_probe_xdl_hazards": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
     "t2o_probe_posf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
                                       ctypes.c_void_p]),
+    "t2o_probe_lds_fill": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]),
+    "t2o_probe_lds_census": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "t2o_bf_swz": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "t2o_env_run": (ctypes.c_int, [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int64] +
                     [ctypes.c_int] * 6 + [ctypes.c_uint64, ctypes.c_void_p]),
@@ -216,7 +218,7 @@ EXPORTS = {
 # exports only tests / tools call (never on the product path), and the newest
 # reporting export: an older build loaded under A/B timing (T2O_LIB) may lack them
 _DIAGNOSTIC = {"t2o_bf_swz", "t2o_probe_lane_ops", "t2o_probe_scatter_ops", "t2o_probe_posf", "t2o_probe_xdl_hazards",
-               "t2o_layout_instance",
+               "t2o_probe_lds_fill", "t2o_probe_lds_census", "t2o_layout_instance",
                "t2o_abi_version"}
 # the logged statistics, the Q(λ) targets and the RMSprop step (same ABI version:
 # nothing existing moved), which a build from before them lacks; calling one on such

@@ -212,3 +212,52 @@ extern "C" int t2o_probe_xdl_hazards(const float* in, float* out, int nwaves, vo
   hipLaunchKernelGGL(probe_xdl_kernel, dim3(nwaves), dim3(64), 0, (hipStream_t)stream, in, out, nwaves);
   return (int)hipGetLastError();
 }
+
+// Stale-LDS probes (tests/lds_fill.py, tests/test_gpu_stale_lds.py).  Both take the
+// whole 160 KB of dynamic LDS a mixer launch can ask for (mix_pick's CAP, raised the
+// way mix_launch raises it), so one workgroup fits per CU.  The fill stores `word`
+// into every 32-bit word of its allocation and exits: a kernel launched after it
+// that reads an LDS word it never wrote reads `word`.  The census writes nothing to
+// LDS and counts, per workgroup, the words that differ from `word`.
+namespace {
+constexpr size_t LDS_PROBE_BYTES = 160 * 1024;  // mix_pick's CAP
+constexpr int LDS_PROBE_WORDS = (int)(LDS_PROBE_BYTES / 4);
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__global__ __launch_bounds__(256) void probe_lds_fill_kernel(uint32_t word) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char probe_lds[];
+  // volatile: nothing in this kernel reads the words back, and the stores must stay
+  typedef volatile __attribute__((address_space(3))) u32x4 lds_u32x4;
+  lds_u32x4* p = (lds_u32x4*)probe_lds;
+  const u32x4 v{word, word, word, word};
+  for (int i = threadIdx.x; i < LDS_PROBE_WORDS / 4; i += 256) p[i] = v;
+}
+
+__global__ __launch_bounds__(64) void probe_lds_census_kernel(uint32_t word, int32_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char probe_lds[];
+  typedef const volatile __attribute__((address_space(3))) uint32_t lds_u32;
+  lds_u32* p = (lds_u32*)probe_lds;
+  int n = 0;
+  for (int i = threadIdx.x; i < LDS_PROBE_WORDS; i += 64) n += p[i] != word;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m);  // cross-lane, no LDS word written
+  if (threadIdx.x == 0) out[blockIdx.x] = n;
+}
+}  // namespace
+
+extern "C" int t2o_probe_lds_fill(uint32_t word, int workgroups, void* stream) {
+  if (workgroups < 1) return T2O_EINVAL;
+  (void)hipFuncSetAttribute((const void*)probe_lds_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)LDS_PROBE_BYTES);
+  hipLaunchKernelGGL(probe_lds_fill_kernel, dim3(workgroups), dim3(256), LDS_PROBE_BYTES, (hipStream_t)stream, word);
+  return (int)hipGetLastError();
+}
+
+extern "C" int t2o_probe_lds_census(uint32_t word, int workgroups, int32_t* out, void* stream) {
+  if (!out || workgroups < 1) return T2O_EINVAL;
+  (void)hipFuncSetAttribute((const void*)probe_lds_census_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)LDS_PROBE_BYTES);
+  hipLaunchKernelGGL(probe_lds_census_kernel, dim3(workgroups), dim3(64), LDS_PROBE_BYTES, (hipStream_t)stream, word,
+                     out);
+  return (int)hipGetLastError();
+}

@@ -741,6 +741,28 @@ def select_actions(q, avail, epsilon=0.0, seed=0, counter=0, out=None):
     return out
 
 
+def _cu_count():
+    return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+
+
+def lds_fill(word, workgroups=None):
+    """Diagnostic (include/t2omca.h t2o_probe_lds_fill): `workgroups` workgroups of one
+    per CU (160 KB of dynamic LDS each; default 4x the CU count) store the 32-bit
+    `word` into every word of their LDS, on the current stream."""
+    n = 4 * _cu_count() if workgroups is None else int(workgroups)
+    check(lib().t2o_probe_lds_fill(int(word) & 0xFFFFFFFF, n, stream_ptr()), "probe_lds_fill")
+
+
+def lds_census(word, workgroups=None):
+    """Diagnostic (t2o_probe_lds_census): int32 [workgroups] (default the CU count),
+    per workgroup the number of words of its 160 KB of LDS that differ from `word`;
+    the kernel writes nothing to LDS."""
+    n = _cu_count() if workgroups is None else int(workgroups)
+    out = torch.empty(n, dtype=torch.int32, device="cuda")
+    check(lib().t2o_probe_lds_census(int(word) & 0xFFFFFFFF, n, ptr(out), stream_ptr()), "probe_lds_census")
+    return out
+
+
 def obs_expand(wire, snap_n, snap, out=None, out64=None):
     """Dense normalised obs from the compact wire format (SURVEY.md §8 f3,
     include/t2omca.h t2o_obs_expand).  wire int32 [B, T1, A, 4] (episode / step
